@@ -527,6 +527,61 @@ int st_batched_tracker_step(StBatchedTracker* t, const int32_t* frame_ids_dev, c
                             const int32_t* counts_dev, void* state_dev, void* scratch_dev, float* out_rows_dev,
                             int64_t* out_ids_dev, int32_t* out_counts_dev, int32_t* status_dev, st_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * 10. Mesh-Affine camera-motion compensation (CMC) of the tracker (reference OCSORTTracker_Disparity(cmc=dict(
+ *     method='glme_affine', glme=dict(step, winsize, ransac_thr, min_inlier_ratio)))): the estimate on the device
+ *     (csrc/cmc_flow.hip; every OpenCV rule restated [upstream-memory], see DESIGN.md "Camera-motion compensation"),
+ *     the application to the Kalman states in the tracker routines of section 8.
+ *   front    frames -> equalised 255 x 255 uint8 grey planes (crop to (h, w), BGR -> RGB, 8-bit INTER_LINEAR resize,
+ *            RGB2GRAY, equalizeHist), one workgroup per frame.  From N separate uint8 (3, fh, fw) device frames (host
+ *            array of device pointers, as st_pack_raw_frames) or from a padded fp32 (N, 3, H, W) batch (values cast
+ *            to uint8); both give the same planes.
+ *   flow     plane pairs (prev[n], curr[n]) -> dense Farneback flow (N, 255, 255, 2) fp32 (pyr_scale 0.5, levels 5,
+ *            iterations 3, poly_n 5, poly_sigma 1.2, flags 0); levels_out (optional): every pyramid level's final flow,
+ *            levels finest first, (N, sum of side^2, 2) (st_cmc_num_levels gives the sides).
+ *   estimate plane pairs -> warps (N, ST_CMC_WARP_FLOATS) = {valid, inlier ratio, a00, a01, a02, a10, a11, a12}
+ *            (the 2 x 3 warp in the coordinates of the (img_h, img_w) crop), via flow, per-cell medians and a
+ *            deterministic exhaustive consensus similarity fit (stated deviation from cv2's RANSAC); mesh_out
+ *            (optional, N x points x 4: src x, y, dst x, y) and inliers_out (optional, N x points uint8).
+ *   ws: caller-owned device workspace of st_cmc_workspace_bytes(N).  Enqueued on `stream`, no host sync.
+ * ---------------------------------------------------------------------- */
+#define ST_CMC_SIDE 255
+#define ST_CMC_WARP_FLOATS 8
+typedef struct StCmcParams {
+  int struct_size;        /* sizeof(StCmcParams) */
+  int step;               /* mesh cell side (8..16; reference default 16) */
+  int winsize;            /* Farneback box window (odd; default 31) */
+  float ransac_thr;       /* inlier: squared residual <= ransac_thr^2 (default 5.0) */
+  float min_inlier_ratio; /* valid = inliers / points >= this (default 0.3) */
+} StCmcParams;
+int st_cmc_num_levels(int* sides);
+size_t st_cmc_workspace_bytes(int N);
+int st_cmc_front_u8(const void* const* frames_u8_dev_ptrs_host, int N, int fh, int fw, int h, int w, void* planes_dev,
+                    st_stream_t stream);
+int st_cmc_front_f32(const float* batch_dev, int N, int H, int W, int h, int w, void* planes_dev, st_stream_t stream);
+int st_cmc_flow(const void* prev_planes_dev, const void* curr_planes_dev, int N, int winsize, void* ws, size_t ws_bytes,
+                float* flow_out_dev, float* levels_out_dev, st_stream_t stream);
+int st_cmc_estimate(const void* prev_planes_dev, const void* curr_planes_dev, int N, int img_h, int img_w,
+                    const StCmcParams* params, void* ws, size_t ws_bytes, float* warps_out_dev, float* mesh_out_dev,
+                    unsigned char* inliers_out_dev, st_stream_t stream);
+/* The tracker step of section 8 with camera-motion compensation: `warp` (2 x 3, row-major, float64) is applied to every
+ * confirmed track's Kalman state right after the predict (reference gmc.py:20-45: mean[0:2] = R mean[0:2] + t,
+ * mean[4:6] = R mean[4:6], mean[3], mean[7] *= s = sqrt(max(det R, 1e-12)), cov = M cov M^T); NULL = no warp.  The
+ * caller decides, as the reference does, that a warp exists only for a frame of the non-empty branch
+ * (st_tracker_cmc_needed). */
+int st_tracker_cmc_needed(const StTracker* t, int frame_id, int n);
+int st_tracker_track_cmc(StTracker* t, int frame_id, const float* dets, int n, const double* warp, float* out_rows,
+                         int64_t* out_ids, int cap, int* out_n);
+/* st_tracker_track_records with per-frame warps.  warps (F, ST_CMC_WARP_FLOATS) as st_cmc_estimate writes them,
+ * warp_src[f] = frame id of the image the warp of frame f was estimated FROM (-1: none).  *cmc_prev (in / out) = frame
+ * id of the tracker's previous CMC image (-1: none; frame id 0 resets it).  A frame of the non-empty branch uses
+ * warps[f] when warp_src[f] == *cmc_prev, no warp when *cmc_prev == -1, and otherwise STOPS: the call returns ST_OK
+ * with *stop_at = f (else F) and out_counts written for frames < f; the caller estimates the pair (*cmc_prev, frame f),
+ * puts it in warps[f] / warp_src[f] and calls again from frame f. */
+int st_tracker_track_records_cmc(StTracker* t, const int* frame_ids, const float* records, int F, int rows_per_frame,
+                                 int cols, const float* warps, const int* warp_src, int* cmc_prev, float* out_rows,
+                                 int64_t* out_ids, int cap, int* out_counts, int* stop_at);
+
 /* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call

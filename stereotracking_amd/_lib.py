@@ -53,6 +53,11 @@ class StTrackerConfig(C.Structure):
     ]
 
 
+class StCmcParams(C.Structure):
+    _fields_ = [('struct_size', C.c_int), ('step', C.c_int), ('winsize', C.c_int), ('ransac_thr', C.c_float),
+                ('min_inlier_ratio', C.c_float)]
+
+
 class StDecodeDesc(C.Structure):
     _fields_ = [
         ('struct_size', C.c_int), ('batch', C.c_int), ('num_levels', C.c_int),
@@ -129,6 +134,16 @@ _PROTOS = {
     'st_tracker_reset': (_i, [_vp]),
     'st_tracker_track': (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, C.POINTER(_i)]),
     'st_tracker_track_records': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    'st_tracker_cmc_needed': (_i, [_vp, _i, _i]),
+    'st_tracker_track_cmc': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    'st_tracker_track_records_cmc': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, C.POINTER(_i), _vp, _vp, _i, _vp,
+                                          C.POINTER(_i)]),
+    'st_cmc_num_levels': (_i, [_vp]),
+    'st_cmc_workspace_bytes': (_sz, [_i]),
+    'st_cmc_front_u8': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'st_cmc_front_f32': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'st_cmc_flow': (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    'st_cmc_estimate': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(StCmcParams), _vp, _sz, _vp, _vp, _vp, _vp]),
     'st_tracker_num_tracks': (_i, [_vp]),
     'st_tracker_next_id': (C.c_longlong, [_vp]),
     'st_tracker_get_track': (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),

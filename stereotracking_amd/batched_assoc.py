@@ -22,7 +22,10 @@ class BatchedGpuTracker:
 
     def __init__(self, batch, max_tracks=128, max_dets=512, device=None, obj_score_thr=0.3, init_track_thr=0.7,
                  weight_iou_with_det_scores=True, match_iou_thr=0.3, num_tentatives=3, vel_consist_weight=0.2,
-                 vel_delta_t=3, num_frames_retain=10):
+                 vel_delta_t=3, num_frames_retain=10, cmc=None):
+        if cmc is not None:
+            raise NotImplementedError('camera-motion compensation (cmc) is not supported by the batched GPU association; '
+                                      'use OCSORTTracker_Disparity (host tracker) for a tracker with cmc')
         self.lib = _lib.load()
         self.batch, self.max_tracks, self.max_dets = int(batch), int(max_tracks), int(max_dets)
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())

@@ -297,7 +297,46 @@ struct StTracker {
     (void)st_lapjv_extended(cost.data(), R, Cn, 1.0 - (double)cfg.match_iou_thr, x.data(), det_to_row.data());
   }
 
-  int track(int frame_id, const float* dets, int n, float* out_rows, int64_t* out_ids, int cap, int* out_n) {
+  // camera-motion compensation of a confirmed track's Kalman state (reference gmc.py:20-45), float64
+  static void apply_warp(KState& s, const double* W) {
+    const double R[4] = {W[0], W[1], W[3], W[4]}, t[2] = {W[2], W[5]};
+    const double det = R[0] * R[3] - R[1] * R[2];
+    const double sc = std::sqrt(det > 1e-12 ? det : 1e-12);
+    double m[8];
+    std::memcpy(m, s.mean, sizeof(m));
+    m[0] = R[0] * s.mean[0] + R[1] * s.mean[1] + t[0];
+    m[1] = R[2] * s.mean[0] + R[3] * s.mean[1] + t[1];
+    m[3] = s.mean[3] * sc;
+    m[4] = R[0] * s.mean[4] + R[1] * s.mean[5];
+    m[5] = R[2] * s.mean[4] + R[3] * s.mean[5];
+    m[7] = s.mean[7] * sc;
+    std::memcpy(s.mean, m, sizeof(m));
+    double M[64] = {};
+    for (int i = 0; i < 8; ++i) M[i * 8 + i] = 1.0;
+    M[0] = R[0]; M[1] = R[1]; M[8] = R[2]; M[9] = R[3];
+    M[4 * 8 + 4] = R[0]; M[4 * 8 + 5] = R[1]; M[5 * 8 + 4] = R[2]; M[5 * 8 + 5] = R[3];
+    M[3 * 8 + 3] = sc; M[7 * 8 + 7] = sc;
+    double tmp[64], out[64];     // (M cov) M^T, as numpy's R8x8.dot(cov).dot(R8x8.T)
+    for (int i = 0; i < 8; ++i)
+      for (int j = 0; j < 8; ++j) {
+        double a = 0;
+        for (int k = 0; k < 8; ++k) a += M[i * 8 + k] * s.cov[k * 8 + j];
+        tmp[i * 8 + j] = a;
+      }
+    for (int i = 0; i < 8; ++i)
+      for (int j = 0; j < 8; ++j) {
+        double a = 0;
+        for (int k = 0; k < 8; ++k) a += tmp[i * 8 + k] * M[j * 8 + k];
+        out[i * 8 + j] = a;
+      }
+    std::memcpy(s.cov, out, sizeof(out));
+  }
+
+  // the reference estimates (and moves its previous CMC image) only in the non-empty branch (:383-445)
+  bool nonempty_branch(int frame_id, int n) const { return frame_id != 0 && !tracks.empty() && n > 0; }
+
+  int track(int frame_id, const float* dets, int n, float* out_rows, int64_t* out_ids, int cap, int* out_n,
+            const double* warp = nullptr) {
     if (frame_id == 0) reset();
     std::vector<int> order;            // detections of the output, in output order
     std::vector<int64_t> ids;
@@ -320,6 +359,8 @@ struct StTracker {
         if (t.tracked) t.saved = t.kf;
         kf_predict(t.kf);
       }
+      if (warp)
+        for (int k : confirmed) apply_warp(tracks[k].kf, warp);
       std::vector<int> matched_det, matched_trk;    // in the order the reference concatenates them
       std::vector<int32_t> d2r;
       auto apply = [&](const std::vector<int>& tidx, std::vector<int>& pool) {
@@ -411,9 +452,11 @@ extern "C" int st_tracker_track(StTracker* t, int frame_id, const float* dets, i
   return t->track(frame_id, dets, n, out_rows, out_ids, cap, out_n);
 }
 
-extern "C" int st_tracker_track_records(StTracker* t, const int* frame_ids, const float* records, int F,
-                                        int rows_per_frame, int cols, float* out_rows, int64_t* out_ids, int cap,
-                                        int* out_counts) {
+namespace {
+// st_tracker_track_records(_cmc): warps == nullptr = no camera-motion compensation
+int track_records(StTracker* t, const int* frame_ids, const float* records, int F, int rows_per_frame, int cols,
+                  const float* warps, const int* warp_src, int* cmc_prev, float* out_rows, int64_t* out_ids, int cap,
+                  int* out_counts, int* stop_at) {
   using namespace st;
   if (!t || !frame_ids || !records || !out_counts)
     return set_error(ST_ERR_INVALID, "st_tracker_track_records: null argument");
@@ -439,9 +482,28 @@ extern "C" int st_tracker_track_records(StTracker* t, const int* frame_ids, cons
       d[0] = r[8]; d[1] = r[9]; d[2] = r[10]; d[3] = r[11];   // the depth-SCALED box (ocsort_disparity.py:82-86)
       d[4] = r[4]; d[5] = r[5]; d[6] = r[6]; d[7] = r[7];
     }
+    double wbuf[6];
+    const double* warp = nullptr;
+    if (warps) {
+      if (frame_ids[f] == 0) *cmc_prev = -1;                       // reset_cmc() on the first frame (:385-387)
+      if (t->nonempty_branch(frame_ids[f], k)) {
+        if (*cmc_prev != -1) {
+          if (warp_src[f] != *cmc_prev) {                           // the speculative pair is not (previous CMC image, f)
+            *stop_at = f;
+            return ST_OK;
+          }
+          const float* w = warps + (size_t)f * ST_CMC_WARP_FLOATS;
+          if (w[0] != 0.f) {
+            for (int i = 0; i < 6; ++i) wbuf[i] = (double)w[2 + i];
+            warp = wbuf;
+          }
+        }
+        *cmc_prev = frame_ids[f];                                   // estimate_camera_motion stores this image
+      }
+    }
     float* o = out_rows + (size_t)f * cap * 8;
     int n = 0;
-    ST_CHECK(t->track(frame_ids[f], dets.data(), k, o, out_ids + (size_t)f * cap, cap, &n));
+    ST_CHECK(t->track(frame_ids[f], dets.data(), k, o, out_ids + (size_t)f * cap, cap, &n, warp));
     // scale_bbox(track_bboxes, 1 / scales) (ocsort_disparity.py:95-97, trackers/utils.py:58-73) as the same fp32
     // single operations torch evaluates (this file is built with -ffp-contract=off)
     for (int i = 0; i < n; ++i) {
@@ -453,7 +515,40 @@ extern "C" int st_tracker_track_records(StTracker* t, const int* frame_ids, cons
     }
     out_counts[f] = n;
   }
+  if (stop_at) *stop_at = F;
   return ST_OK;
+}
+}  // namespace
+
+extern "C" int st_tracker_track_records(StTracker* t, const int* frame_ids, const float* records, int F,
+                                        int rows_per_frame, int cols, float* out_rows, int64_t* out_ids, int cap,
+                                        int* out_counts) {
+  return track_records(t, frame_ids, records, F, rows_per_frame, cols, nullptr, nullptr, nullptr, out_rows, out_ids,
+                       cap, out_counts, nullptr);
+}
+
+extern "C" int st_tracker_track_records_cmc(StTracker* t, const int* frame_ids, const float* records, int F,
+                                            int rows_per_frame, int cols, const float* warps, const int* warp_src,
+                                            int* cmc_prev, float* out_rows, int64_t* out_ids, int cap, int* out_counts,
+                                            int* stop_at) {
+  using namespace st;
+  if (!warps || !warp_src || !cmc_prev || !stop_at)
+    return set_error(ST_ERR_INVALID, "st_tracker_track_records_cmc: null argument");
+  return track_records(t, frame_ids, records, F, rows_per_frame, cols, warps, warp_src, cmc_prev, out_rows, out_ids,
+                       cap, out_counts, stop_at);
+}
+
+extern "C" int st_tracker_cmc_needed(const StTracker* t, int frame_id, int n) {
+  return t && t->nonempty_branch(frame_id, n) ? 1 : 0;
+}
+
+extern "C" int st_tracker_track_cmc(StTracker* t, int frame_id, const float* dets, int n, const double* warp,
+                                    float* out_rows, int64_t* out_ids, int cap, int* out_n) {
+  using namespace st;
+  if (!t || !out_n) return set_error(ST_ERR_INVALID, "st_tracker_track_cmc: null argument");
+  ST_REQUIRE(n >= 0 && cap >= 0 && (n == 0 || dets) && (cap == 0 || (out_rows && out_ids)),
+             "st_tracker_track_cmc: bad buffers");
+  return t->track(frame_id, dets, n, out_rows, out_ids, cap, out_n, warp);
 }
 
 extern "C" int st_tracker_num_tracks(const StTracker* t) { return t ? (int)t->tracks.size() : 0; }

@@ -569,8 +569,74 @@ class OCSORT_Disparity(nn.Module):
             holder.update(ctx=ctx, disp=out['disp_postp'], disp_slot=runner.pipes[ctx].disp_slot if stereo else None, host=host, slot=slot)
             return out
         _, ev = runner.submit(a, right=b if stereo else None, disp_postp=None if stereo else b, post=post)
+        cmc = self._cmc_submit(st, s, e) if getattr(self.tracker, 'with_cmc', False) else None
         self.timings['submit_s'] += time.perf_counter() - ts
-        st['jobs'][ci] = dict(s=s, e=e, ev=ev, **holder)
+        st['jobs'][ci] = dict(s=s, e=e, ev=ev, cmc=cmc, **holder)
+
+    # ---- camera-motion compensation of the tracker (cmc=dict(method='glme_affine')) ---------------------------------
+    def _cmc_submit(self, st, s, e):
+        """On a side stream, from the chunk's input already on the device: the grey planes of frames [s, e) and the
+        SPECULATIVE warps of the consecutive pairs (n - 1, n) (the first frame's pair reaches back to the last frame of
+        the chunk submitted before).  The warps travel to the host beside the chunk's records; the association uses
+        one only when its pair is (previous CMC image, frame) - see _cmc_track_records."""
+        from . import cmc
+        dev, img = st['dev'], st['img']
+        metas = [st['data_samples'][n].metainfo for n in range(s, e)]
+        shapes = {tuple(int(v) for v in m['img_shape'][:2]) for m in metas}
+        if len(shapes) != 1:
+            raise NotImplementedError('camera-motion compensation over a chunk needs one img_shape')
+        hw = shapes.pop()
+        fids = [int(m.get('frame_id', -1)) for m in metas]
+        cs = self._staging.get(('cmc_stream', dev))
+        if cs is None:
+            cs = self._staging[('cmc_stream', dev)] = torch.cuda.Stream(device=dev)
+        cs.wait_stream(torch.cuda.current_stream(dev))       # the chunk's input is written on the current stream
+        tail = self._staging.get('cmc_tail')                  # (planes, index, frame id, img_shape) of the last chunk
+        k = e - s
+        with torch.cuda.stream(cs):
+            planes = torch.empty(k + 1, cmc.SIDE, cmc.SIDE, dtype=torch.uint8, device=dev)
+            cmc.front(img.frames[s:e] if isinstance(img, RawFrames) else img[s:e], hw[0], hw[1], out=planes[1:])
+            if tail is not None and tail[3] == hw:
+                planes[0].copy_(tail[0][tail[1]])
+                src0 = tail[2]
+            else:
+                planes[0].copy_(planes[1])
+                src0 = -2                                     # matches no frame: computed on demand if needed
+            warps = cmc.estimate(planes[:-1], planes[1:], hw[0], hw[1], self.tracker.cmc_params)
+            host = torch.empty(k, cmc.WARP_FLOATS, pin_memory=True)
+            host.copy_(warps, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(cs)
+        self._staging['cmc_tail'] = (planes, k, fids[-1], hw)
+        return dict(planes=planes, host=host, ev=ev, fids=fids, warp_src=[src0] + fids[:-1], hw=hw, stream=cs)
+
+    def _cmc_plane(self, job, fid):
+        """Grey plane (1, 255, 255) of frame `fid`: from the chunk, else the tracker's previous CMC image."""
+        if fid in job['fids']:
+            i = job['fids'].index(fid) + 1
+            return job['planes'][i:i + 1]
+        if self.tracker.prev_cmc_fid == fid and self.tracker.prev_cmc_img is not None:
+            return self.tracker.prev_cmc_img
+        raise RuntimeError(f'camera-motion compensation: no plane of frame {fid}')
+
+    def _cmc_track_records(self, fids, chunk_np, job):
+        """The chunk's association in native calls (st_tracker_track_records_cmc): a frame whose speculative pair is
+        not (previous CMC image, frame) stops the call; that pair is estimated on demand and the call resumes there."""
+        from . import cmc
+        trk = self.tracker
+        warps = job['host'].numpy().copy()
+        src = np.asarray(job['warp_src'], np.int32)
+
+        def on_demand(f, prev_fid):
+            with torch.cuda.stream(job['stream']):     # the copy too: it must follow the estimate on the CMC stream
+                w = cmc.estimate(self._cmc_plane(job, prev_fid), job['planes'][f + 1:f + 2], job['hw'][0], job['hw'][1],
+                                 trk.cmc_params)
+                return w[0].cpu().numpy()
+
+        out = trk.track_records(fids, chunk_np, cmc=(warps, src, on_demand))
+        prev = trk.prev_cmc_fid
+        trk.prev_cmc_img = None if prev == -1 else self._cmc_plane(job, prev)
+        return out
 
     def finish(self, st, lookahead=None):
         """Run call `st` to completion and return its samples.  `lookahead`: the begin() state of the NEXT call on the
@@ -630,7 +696,11 @@ class OCSORT_Disparity(nn.Module):
                 # (numpy copies: a torch CPU op above ~32 K elements wakes the whole intra-op thread pool - tens of
                 # milliseconds on a 256-core host whose process owns a 16-core share - for a 400 KB memcpy)
                 chunk_np = rec[:e - s].numpy().copy()  # the staging buffer is reused by a later chunk
-                trows, tids, tcnt = self.tracker.track_records(fids, chunk_np)
+                if job['cmc'] is not None:
+                    job['cmc']['ev'].synchronize()     # the chunk's speculative warps (long done: ~0.2 ms of work)
+                    trows, tids, tcnt = self._cmc_track_records(fids, chunk_np, job['cmc'])
+                else:
+                    trows, tids, tcnt = self.tracker.track_records(fids, chunk_np)
                 det_labels = torch.from_numpy(chunk_np[:, 1:, 5].astype(np.int64))
                 det_prior = torch.from_numpy(chunk_np[:, 1:, 12].astype(np.int64))
                 trk_labels = torch.from_numpy(trows[:, :, 5].astype(np.int64))
@@ -651,6 +721,9 @@ class OCSORT_Disparity(nn.Module):
                     tracks.instances_id = tids[i, :m]
                     tracks_of.append(tracks)
             else:
+              cj = job['cmc']
+              if cj is not None:
+                  cj['ev'].synchronize()
               for n in range(s, e):
                 r = rec[n - s]
                 k, cap = int(r[0, 0]), int(r[0, 1])
@@ -663,7 +736,12 @@ class OCSORT_Disparity(nn.Module):
                 # reference :82-86: the tracker consumes the depth-SCALED boxes + scales + depth
                 sample.pred_det_instances = InstanceData(bboxes=rows[:, 8:12], scores=rows[:, 4], labels=labels,
                                                          scales=rows[:, 7], depth=rows[:, 6])
-                tracks = self.tracker.track(model=self, img=None, feats=None, data_sample=sample, **kwargs)
+                cimg = None
+                if cj is not None:
+                    from .cmc import CmcFrame
+                    i = n - s
+                    cimg = CmcFrame(cj['planes'][i + 1:i + 2], cj['fids'][i], cj['host'][i].numpy(), cj['warp_src'][i])
+                tracks = self.tracker.track(model=self, img=cimg, feats=None, data_sample=sample, **kwargs)
                 tracks['bboxes'] = scale_bbox(tracks.bboxes, 1 / tracks.scales)      # unscale (:95-97)
                 sample.pred_det_instances = InstanceData(bboxes=rows[:, 0:4].clone(), scores=rows[:, 4].clone(),
                                                          labels=labels, prior_idx=rows[:, 12].long())   # (:107-108)

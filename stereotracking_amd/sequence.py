@@ -320,6 +320,10 @@ def track_gathered(dets, counts, num_frames, tracker, model):
     """CPU association over gathered frame records in frame order -> list of InstanceData per frame
     (boxes unscaled back, as OCSORT_Disparity.predict does at ocsort_disparity.py:95-97).  `counts` is
     ignored (the records carry their own; kept in the signature for callers that still pass it)."""
+    if getattr(tracker, 'with_cmc', False):
+        # consecutive frames may have been detected on different ranks: no rank holds the image pairs
+        raise NotImplementedError('camera-motion compensation (tracker cmc) is not supported by the sharded driver; '
+                                  'run the video through OCSORT_Disparity.predict on one device')
     dets = dets.cpu()
     results = []
     for t in range(num_frames):

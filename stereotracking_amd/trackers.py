@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import cmc as _cmc
 from .registry import MODELS
 from .structures import InstanceData
 
@@ -107,12 +108,54 @@ class OCSORTTracker_Disparity:
         self.num_frames_retain = num_frames_retain
         if momentums is not None:
             raise NotImplementedError('momentum buffers are not used by the stereo configs')
+        # Mesh-Affine camera-motion compensation (reference :62-76): estimated on the device (cmc.py,
+        # csrc/cmc_flow.hip), applied to the confirmed tracks' Kalman states right after the predict
+        self.cmc_cfg = cmc
         method = cmc.get('method') if cmc is not None else None
-        if method is not None:
-            if method != 'glme_affine':
-                raise ValueError(f"Unknown cmc method '{method}', expected 'glme_affine' or None.")
-            raise NotImplementedError('Mesh-Affine CMC needs OpenCV (absent); the shipped config runs with cmc=None')
+        if method is None:
+            self.cmc_mode = None
+        elif method == 'glme_affine':
+            self.cmc_mode = 'mesh_affine'
+            self.cmc_params = _cmc.glme_params(cmc.get('glme'))
+        else:
+            raise ValueError(f"Unknown cmc method '{method}', expected 'glme_affine' or None.")
+        self.reset_cmc()
         self.reset()
+
+    # ---- camera-motion compensation (reference :78-97) ---------------------------------------------------------
+    @property
+    def with_cmc(self):
+        return self.cmc_mode is not None
+
+    def reset_cmc(self):
+        """Forget the previous CMC image (the first frame of a video)."""
+        self.prev_cmc_img = None         # grey plane (1, 255, 255) uint8 on the device
+        self.prev_cmc_fid = -1
+
+    def estimate_camera_motion(self, img, metainfo):
+        """The 2 x 3 background warp from the previous CMC image to `img` (float32 numpy) or None; `img` becomes the
+        previous CMC image.  img: the (1, 3, H, W) fp32 / uint8 CUDA batch the tracker receives (cropped to
+        metainfo['img_shape']), or a cmc.CmcFrame of the shell's chunk path (plane computed with its chunk, with the
+        speculative warp of the pair (warp_src, this frame), used when warp_src is the previous CMC image)."""
+        if self.cmc_mode != 'mesh_affine':
+            return None
+        fid = int(metainfo.get('frame_id', -1))
+        h, w = (int(v) for v in metainfo['img_shape'][:2])
+        if isinstance(img, _cmc.CmcFrame):
+            plane, fid = img.plane, img.fid
+        else:
+            if img is None:
+                raise ValueError('the tracker has CMC on: track() needs the frame (img)')
+            plane = _cmc.front(img[:1], h, w)
+        warp = None
+        if self.prev_cmc_img is not None:
+            if isinstance(img, _cmc.CmcFrame) and img.warp is not None and img.warp_src == self.prev_cmc_fid:
+                row = img.warp
+            else:
+                row = _cmc.estimate(self.prev_cmc_img, plane, h, w, self.cmc_params)[0].cpu().numpy()
+            warp = _cmc.warp_or_none(row)
+        self.prev_cmc_img, self.prev_cmc_fid = plane, fid
+        return warp
 
     # ---- bookkeeping ---------------------------------------------------------------------------
     def reset(self):
@@ -171,11 +214,14 @@ class OCSORTTracker_Disparity:
                             last_frame=lf.value))
         return out
 
-    def track_records(self, frame_ids, records):
+    def track_records(self, frame_ids, records, cmc=None):
         """A CHUNK of frames in one native call (st_tracker_track_records): `records` = host float32 (F, M + 1, 13)
         frame records (pipeline.pack_detections(scaled='both')), `frame_ids` = F ints.
         -> (rows (F, M, 8) float32 [unscaled box, score, label, depth, scale], ids (F, M) int64, counts (F,) int32;
-        -1 = padding frame).  Native backend only."""
+        -1 = padding frame).  Native backend only.
+        cmc (a tracker with CMC): (warps (F, 8) float32, warp_src (F,) int32, on_demand(f, prev_fid) -> (8,) row, f = index in the chunk): the
+        speculative warp of frame f is used when warp_src[f] is the previous CMC image, else on_demand estimates the
+        pair (st_tracker_track_records_cmc stops there and resumes)."""
         if self.backend != 'native':
             raise RuntimeError("track_records needs backend='native'")
         F, R, Cc = records.shape
@@ -184,10 +230,15 @@ class OCSORTTracker_Disparity:
         rows = np.zeros((F, R - 1, 8), np.float32)     # rows past a frame's count stay zero (they are sliced off)
         ids = np.zeros((F, R - 1), np.int64)
         counts = np.empty(F, np.int32)
-        rc = _lib.load().st_tracker_track_records(self._handle(), fid.ctypes.data_as(C.c_void_p),
-                                                  rec.ctypes.data_as(C.c_void_p), F, R, Cc,
-                                                  rows.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
-                                                  R - 1, counts.ctypes.data_as(C.c_void_p))
+        if self.with_cmc:
+            if cmc is None:
+                raise ValueError('the tracker has CMC on: track_records needs the chunk\'s warps (cmc=...)')
+            rc = self._track_records_cmc(fid, rec, rows, ids, counts, *cmc)
+        else:
+            rc = _lib.load().st_tracker_track_records(self._handle(), fid.ctypes.data_as(C.c_void_p),
+                                                      rec.ctypes.data_as(C.c_void_p), F, R, Cc,
+                                                      rows.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
+                                                      R - 1, counts.ctypes.data_as(C.c_void_p))
         if rc == -4:   # ST_ERR_WORKSPACE: a frame kept more boxes than the record holds
             from .dist import DetectionOverflow
             raise DetectionOverflow(_lib.load().st_last_error().decode() + '; build the model with a larger max_det')
@@ -195,7 +246,28 @@ class OCSORTTracker_Disparity:
         self.num_tracks = int(_lib.load().st_tracker_next_id(self._native))
         return rows, ids, counts
 
-    def _track_native(self, data_sample):
+    def _track_records_cmc(self, fid, rec, rows, ids, counts, warps, warp_src, on_demand):
+        F, R, Cc = rec.shape
+        warps = np.ascontiguousarray(warps, dtype=np.float32)
+        src = np.ascontiguousarray(warp_src, dtype=np.int32)
+        prev, stop = C.c_int(self.prev_cmc_fid), C.c_int()
+        p = lambda a, i: a[i:].ctypes.data_as(C.c_void_p)  # noqa: E731
+        f = 0
+        while True:
+            rc = _lib.load().st_tracker_track_records_cmc(self._handle(), p(fid, f), p(rec, f), F - f, R, Cc,
+                                                          p(warps, f), p(src, f), C.byref(prev), p(rows, f), p(ids, f),
+                                                          R - 1, p(counts, f), C.byref(stop))
+            if rc != 0 or f + stop.value >= F:
+                break
+            f += stop.value                      # frame f needs the pair (previous CMC image, f): estimate it now
+            warps[f] = on_demand(f, prev.value)
+            src[f] = prev.value
+        self.prev_cmc_fid = prev.value
+        if rc == 0 and self.prev_cmc_fid == -1:
+            self.prev_cmc_img = None
+        return rc
+
+    def _track_native(self, data_sample, img=None):
         det = data_sample.pred_det_instances
         dev = det.bboxes.device
         n = len(det.bboxes)
@@ -210,9 +282,22 @@ class OCSORTTracker_Disparity:
         ids = np.empty(n, np.int64)
         k = C.c_int()
         frame_id = int(data_sample.metainfo.get('frame_id', -1))
-        _lib.check(_lib.load().st_tracker_track(self._handle(), frame_id, rows.ctypes.data_as(C.c_void_p), n,
-                                                out.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), n,
-                                                C.byref(k)), 'st_tracker_track')
+        if not self.with_cmc:
+            _lib.check(_lib.load().st_tracker_track(self._handle(), frame_id, rows.ctypes.data_as(C.c_void_p), n,
+                                                    out.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), n,
+                                                    C.byref(k)), 'st_tracker_track')
+        else:
+            if frame_id == 0:
+                self.reset_cmc()
+            warp = None
+            if _lib.load().st_tracker_cmc_needed(self._handle(), frame_id, n):     # the non-empty branch
+                warp = self.estimate_camera_motion(img, data_sample.metainfo)
+            wd = None if warp is None else np.ascontiguousarray(warp, dtype=np.float64)
+            _lib.check(_lib.load().st_tracker_track_cmc(self._handle(), frame_id, rows.ctypes.data_as(C.c_void_p), n,
+                                                        None if wd is None else wd.ctypes.data_as(C.c_void_p),
+                                                        out.ctypes.data_as(C.c_void_p),
+                                                        ids.ctypes.data_as(C.c_void_p), n, C.byref(k)),
+                       'st_tracker_track_cmc')
         k = k.value
         self.num_tracks = int(_lib.load().st_tracker_next_id(self._native))
         t = torch.from_numpy(out[:k])
@@ -352,13 +437,14 @@ class OCSORTTracker_Disparity:
     # ---- main entry ---------------------------------------------------------------------------------------
     def track(self, model, img, feats, data_sample, data_preprocessor=None, rescale=False, **kwargs):
         if self.backend == 'native':
-            return self._track_native(data_sample)
+            return self._track_native(data_sample, img)
         det = data_sample.pred_det_instances
         dev = det.bboxes.device
         fields = {k: det[k].detach().cpu() for k in ('bboxes', 'labels', 'scores', 'scales', 'depth')}
         frame_id = data_sample.metainfo.get('frame_id', -1)
         if frame_id == 0:
             self.reset()
+            self.reset_cmc()
         if not hasattr(self, 'kf'):
             self.kf = model.motion
 
@@ -376,6 +462,8 @@ class OCSORTTracker_Disparity:
             cand = take(keep)                               # detections entering association
             cand_ids = torch.full((cand['bboxes'].size(0),), -1, dtype=fields['labels'].dtype)
 
+            # this frame's background motion, estimated once (reference :428-432), applied right after the predict
+            warp = self.estimate_camera_motion(img, data_sample.metainfo) if self.with_cmc else None
             # KF predict for confirmed tracks (velocity of h zeroed while lost)
             confirmed = self.confirmed_ids
             for i in confirmed:
@@ -385,6 +473,10 @@ class OCSORTTracker_Disparity:
                 if t.tracked:
                     t.saved = (t.mean, t.covariance)
                 t.mean, t.covariance = self.kf.predict(t.mean, t.covariance)
+            if warp is not None:
+                for i in confirmed:
+                    t = self.tracks[i]
+                    t.mean, t.covariance = _cmc.apply_warp(t.mean, t.covariance, warp)
 
             def split(pool, pool_ids, det_to_track, track_ids):
                 """apply one assignment: returns (matched pool, matched ids, rest pool, rest ids)"""
