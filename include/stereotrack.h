@@ -582,6 +582,52 @@ int st_tracker_track_records_cmc(StTracker* t, const int* frame_ids, const float
                                  int cols, const float* warps, const int* warp_src, int* cmc_prev, float* out_rows,
                                  int64_t* out_ids, int cap, int* out_counts, int* stop_at);
 
+/* ------------------------------------------------------------------------
+ * 11. Stereo matching: OpenCV StereoSGBM in mode SGBM_3WAY (the matcher behind the reference's AirDrone disparity PNGs,
+ *     reproducibility.md section 3), restated from OpenCV 4.x [upstream-memory] in csrc/sgbm.hip; the rules are listed in
+ *     tests/sgbm_ref.py and DESIGN.md "Stereo SGBM".  Every stage is integer arithmetic.
+ *   input    N uint8 (3, fh, fw) left / right device frames (host arrays of device pointers, as st_pack_raw_frames),
+ *            or padded fp32 (N, 3, H, W) batches with integral values; the top-left h x w is matched.  BGR; color = 0
+ *            matches the fixed-point BGR2GRAY of the frames.  Both forms give the same bits.
+ *   output   disp_postp (N, 3, H, W) fp32 = max(d16, 0) / 16 in all three channels, 0 outside h x w (the PNG
+ *            loader's convention: invalid -> 0).
+ *   limits   min_disparity 0; num_disparities in {16, 32, 48, 64} and < w; w <= 4096; block_size odd, 1..9;
+ *            pre_filter_cap 1..127; parameter sets whose worst-case aggregated cost
+ *            3 (block_size^2 cn (2 ftzero + 63) + max(P2, P1 + 1)) leaves int16 are refused (ST_ERR_INVALID).
+ *   status   int on the device, written by every call that runs the speckle filter: 0 = every union-find loop
+ *            converged; bit 0 / 1 = a find / link loop reached its bound (the result is then not the spec's).
+ *   ws: caller-owned device workspace of st_sgbm_workspace_bytes(N, h, w, D).  Enqueued on `stream`, no host sync.
+ *   Stage entry points (tests): st_sgbm_match_f32 -> the block-summed cost C (N, h, w - D, D) int16 and / or the int16
+ *   disparity x 16 (N, h, w) after the left-right check, before the median (-16 invalid); st_sgbm_median (3 x 3,
+ *   replicated borders); st_sgbm_speckle (filterSpeckles with newVal -16; out int16 and / or disp_postp, workspace
+ *   2 N h w ints, each 256-byte aligned).
+ * ---------------------------------------------------------------------- */
+typedef struct StSgbmParams {
+  int struct_size;         /* sizeof(StSgbmParams) */
+  int num_disparities;     /* D: 16, 32, 48 or 64 */
+  int block_size;          /* odd */
+  int P1, P2;              /* smoothness penalties; P2 is used as max(P2, P1 + 1) */
+  int disp12_max_diff;     /* <= 0 is taken as 1 */
+  int uniqueness_ratio;    /* percent, 0..99 (0 = no uniqueness test) */
+  int speckle_window_size; /* 0 = no speckle filter */
+  int speckle_range;       /* maxDiff = 16 * speckle_range */
+  int pre_filter_cap;      /* ftzero = max(pre_filter_cap, 15) | 1 */
+  int color;               /* 1: match the 3 BGR channels; 0: grey */
+} StSgbmParams;
+size_t st_sgbm_workspace_bytes(int N, int h, int w, int D);
+int st_sgbm_u8(const void* const* left_ptrs_host, const void* const* right_ptrs_host, int N, int fh, int fw, int h,
+               int w, const StSgbmParams* params, void* ws, size_t ws_bytes, float* disp_postp_dev, int H, int W,
+               int* status_dev, st_stream_t stream);
+int st_sgbm_f32(const float* left_dev, const float* right_dev, int N, int H, int W, int h, int w,
+                const StSgbmParams* params, void* ws, size_t ws_bytes, float* disp_postp_dev, int* status_dev,
+                st_stream_t stream);
+int st_sgbm_match_f32(const float* left_dev, const float* right_dev, int N, int H, int W, int h, int w,
+                      const StSgbmParams* params, void* ws, size_t ws_bytes, int16_t* cost_out_dev,
+                      int16_t* disp_out_dev, st_stream_t stream);
+int st_sgbm_median(const int16_t* in_dev, int N, int h, int w, int16_t* out_dev, st_stream_t stream);
+int st_sgbm_speckle(const int16_t* in_dev, int N, int h, int w, int max_size, int max_diff, void* ws, size_t ws_bytes,
+                    int16_t* out_dev, float* disp_postp_dev, int H, int W, int* status_dev, st_stream_t stream);
+
 /* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call

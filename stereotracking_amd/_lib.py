@@ -58,6 +58,13 @@ class StCmcParams(C.Structure):
                 ('min_inlier_ratio', C.c_float)]
 
 
+class StSgbmParams(C.Structure):
+    _fields_ = [('struct_size', C.c_int), ('num_disparities', C.c_int), ('block_size', C.c_int), ('P1', C.c_int),
+                ('P2', C.c_int), ('disp12_max_diff', C.c_int), ('uniqueness_ratio', C.c_int),
+                ('speckle_window_size', C.c_int), ('speckle_range', C.c_int), ('pre_filter_cap', C.c_int),
+                ('color', C.c_int)]
+
+
 class StDecodeDesc(C.Structure):
     _fields_ = [
         ('struct_size', C.c_int), ('batch', C.c_int), ('num_levels', C.c_int),
@@ -144,6 +151,12 @@ _PROTOS = {
     'st_cmc_front_f32': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'st_cmc_flow': (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     'st_cmc_estimate': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(StCmcParams), _vp, _sz, _vp, _vp, _vp, _vp]),
+    'st_sgbm_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'st_sgbm_u8': (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(StSgbmParams), _vp, _sz, _vp, _i, _i, _vp, _vp]),
+    'st_sgbm_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(StSgbmParams), _vp, _sz, _vp, _vp, _vp]),
+    'st_sgbm_match_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(StSgbmParams), _vp, _sz, _vp, _vp, _vp]),
+    'st_sgbm_median': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'st_sgbm_speckle': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _i, _i, _vp, _vp]),
     'st_tracker_num_tracks': (_i, [_vp]),
     'st_tracker_next_id': (C.c_longlong, [_vp]),
     'st_tracker_get_track': (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),

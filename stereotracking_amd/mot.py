@@ -25,6 +25,7 @@ from .trackers import OCSORTTracker_Disparity  # noqa: F401  (registers the trac
 from .motion import KalmanFilter  # noqa: F401  (registers the motion model)
 from . import detectors  # noqa: F401  (registers detector / backbone / neck / head)
 from . import stereo as _stereo  # noqa: F401  (registers StereoCostVolume)
+from . import sgbm as _sgbm  # noqa: F401  (registers StereoSGBM)
 
 
 def stack_batch(tensors, pad_size_divisor=0, pad_value=0):
@@ -286,7 +287,8 @@ class OCSORT_Disparity(nn.Module):
     per-frame launches, no per-frame syncs.  The association step consumes the frames sequentially on the CPU while
     the GPU works on the following chunks.
 
-    New (optional) constructor arguments next to the reference's: `stereo` (StereoCostVolume config), `dense_batch`,
+    New (optional) constructor arguments next to the reference's: `stereo` (StereoCostVolume or StereoSGBM config; with
+    StereoSGBM the mono detector runs on the SGBM disparity of the left / right frames), `dense_batch`,
     `inflight`, `max_det` (rows of the detection buffer: a capacity, overflow raises) and `results_device`
     ('cpu': results stay where the CPU tracker produced them - the consumers are the host-side evaluator / CSV
     writer; 'input': moved back to the device of the inputs like the reference's tensors)."""
@@ -305,7 +307,7 @@ class OCSORT_Disparity(nn.Module):
             # the full-resolution mode's reduce conv reads the detector's stage-1 features: make_divisible(128, widen)
             import math
             stereo = dict(stereo, feat_channels=int(math.ceil(128 * self.detector.widen_factor / 8) * 8))
-        self.stereo = MODELS.build(stereo) if stereo is not None else None  # StereoCostVolume (new module)
+        self.stereo = MODELS.build(stereo) if stereo is not None else None  # StereoCostVolume / StereoSGBM (new modules)
         if self.stereo is not None and self.detector is not None:
             self.detector.__dict__['stereo'] = self.stereo   # plain reference: registered once, under the shell
         self.dense_batch, self.inflight, self.max_det = int(dense_batch), int(inflight), int(max_det)
@@ -382,6 +384,9 @@ class OCSORT_Disparity(nn.Module):
         ent = self._dense.get(key)
         if ent is None:
             sm = self.stereo
+            sgbm = sm if stereo and isinstance(sm, _sgbm.StereoSGBM) else None
+            if sgbm is not None:    # SGBM disparity feeding the mono detector plan: no cost-volume attributes
+                sm, stereo = None, False
             runner = InflightPipelines(
                 max(1, self.inflight), batch, (key[1], key[2]), det.widen_factor, det.deepen_factor,
                 det.num_classes, stereo=bool(stereo), max_disp=sm.max_disp if stereo else 192,
@@ -393,7 +398,8 @@ class OCSORT_Disparity(nn.Module):
                 split_bf16=self.split_bf16, multi_label=getattr(det, 'multi_label', True),
                 rgb_only=getattr(det, 'rgb_only', False),
                 full_res=bool(getattr(sm, 'full_res', False)) if stereo else False,
-                full_res_channels=(sm.reduce.out_channels if stereo and getattr(sm, 'full_res', False) else 8))
+                full_res_channels=(sm.reduce.out_channels if stereo and getattr(sm, 'full_res', False) else 8),
+                sgbm=sgbm)
             for p in runner.pipes:     # the track-box depth reads run k's disparity while later runs are in flight
                 p.disp_buffers = self.queue_depth + 1
             ent = self._dense[key] = [runner, None]
@@ -520,6 +526,12 @@ class OCSORT_Disparity(nn.Module):
         for m in metas[1:]:
             if tuple(int(v) for v in m.get('ori_shape', ori)[:2]) != ori:
                 raise NotImplementedError('one batched launch plan needs a uniform ori_shape')
+        if stereo and isinstance(self.stereo, _sgbm.StereoSGBM):
+            for m in metas:
+                if 'img_shape' in m and tuple(int(v) for v in m['img_shape'][:2]) != ori:
+                    raise NotImplementedError(
+                        f"StereoSGBM matches at the original resolution: img_shape {tuple(m['img_shape'][:2])} differs "
+                        f"from ori_shape {ori} (the reference matched before resizing; that order is not restated)")
         B = min(self.dense_batch, N)      # a call with fewer frames than dense_batch gets a plan of its own size
         runner = self.dense_runner(ori, stereo, B)
         return dict(img=img, second=second, gt=gt, stereo=stereo, N=N, B=B, runner=runner, dev=img.device,

@@ -93,11 +93,16 @@ class StereoDensePipeline:
     def __init__(self, batch, ori_shape=(720, 1280), widen_factor=0.5, deepen_factor=0.33, num_classes=1,
                  stereo=True, max_disp=192, feat_stride=4, temperature=32.0, score_thr=0.01, iou_thr=0.5,
                  max_det=1000, baseline=0.25, focal_length=640, pad_size_divisor=32, agg_layers=0, agg3d_layers=0,
-                 split_bf16=None, multi_label=True, rgb_only=False, full_res=False, full_res_channels=8):
+                 split_bf16=None, multi_label=True, rgb_only=False, full_res=False, full_res_channels=8, sgbm=None):
         """max_det: rows of the fixed-size detection buffer per frame.  The reference applies NO cap on the
         kept boxes (yolox_style=True => max_per_img = len(results)), so this is a
         capacity, not a threshold: `run()` reports `overflow` whenever a frame kept more boxes than fit, and
-        every consumer in this package (sequence drivers, MOT shell, bench.py) raises on it."""
+        every consumer in this package (sequence drivers, MOT shell, bench.py) raises on it.
+
+        sgbm: a StereoSGBM config dict (or module, whose configuration is copied: every context owns its workspace).
+        The pipeline then takes left + right frames like the stereo mode, computes the disparity with OpenCV's
+        SGBM_3WAY restated on the device (sgbm.py) into the same disp_postp ring, and runs the MONO detector plan
+        (stereo must be False) on img + that disparity - the configuration the reference's detector was trained in."""
         self.lib = _lib.load()
         self.batch = int(batch)
         self.ori_h, self.ori_w = int(ori_shape[0]), int(ori_shape[1])
@@ -105,6 +110,14 @@ class StereoDensePipeline:
         self.height = (self.ori_h + d - 1) // d * d
         self.width = (self.ori_w + d - 1) // d * d
         self.stereo = bool(stereo)
+        self.sgbm = None
+        if sgbm is not None:
+            from .sgbm import StereoSGBM
+            if self.stereo:
+                raise ValueError('sgbm= runs the mono detector plan on the SGBM disparity: pass stereo=False')
+            self.sgbm = StereoSGBM(**(sgbm.config() if isinstance(sgbm, StereoSGBM) else
+                                      {k: v for k, v in sgbm.items() if k != 'type'}))
+        self.takes_right = self.stereo or self.sgbm is not None    # run() needs the right image
         # full_res: the stereo module's full-resolution mode (D = max_disp levels at image resolution, 3-D aggregation
         # only; stereo.py) - north_star's literal D x H x W sizing as a product path
         self.full_res = bool(full_res) and bool(stereo)
@@ -229,7 +242,8 @@ class StereoDensePipeline:
     # ---- the hot path --------------------------------------------------------------------------------
     def disparity(self, img, right):
         """Stereo module: stem+stage1 features of left/right -> cost volume -> soft-argmin ->
-        bilinear x4 -> disp_postp (N,3,H,W) in pixels, 0 outside the original image."""
+        bilinear x4 -> disp_postp (N,3,H,W) in pixels, 0 outside the original image.  With sgbm: StereoSGBM of
+        left/right (RawChunks or fp32 batches) -> disp_postp."""
         b = self._buffers(img.device)
         k = self._disp_turn % len(b['disp_ring'])
         self._disp_turn += 1
@@ -238,7 +252,10 @@ class StereoDensePipeline:
             torch.cuda.current_stream(img.device).wait_event(self.disp_guard[k])
             self.disp_guard[k] = None
         out = b['disp_postp'] = b['disp_ring'][k]
-        self.stereo_module.compute(self.det, img, right, (self.ori_h, self.ori_w), b['disp_lr'], out)
+        if self.sgbm is not None:
+            self.sgbm.compute(img, right, (self.ori_h, self.ori_w), out)
+        else:
+            self.stereo_module.compute(self.det, img, right, (self.ori_h, self.ori_w), b['disp_lr'], out)
         return out
 
     def box_depth(self, disp_postp, boxes, counts, out=None):
@@ -259,12 +276,17 @@ class StereoDensePipeline:
         scaled_boxes, disp_postp, head.  Rows past min(counts, M) are zero (prior_idx -1).  With disp_buffers > 1 the
         stereo module's disp_postp is buffer `self.disp_slot` of the ring (see _buffers)."""
         if isinstance(img, RawChunk):
-            if self.stereo and not isinstance(right, RawChunk):
+            if (self.stereo or self.sgbm is not None) and not isinstance(right, RawChunk):
                 raise ValueError('the stereo pipeline takes left AND right as raw uint8 chunks (or both as fp32 tensors)')
         else:
             _require_cuda(img, 'img')
         b = self._buffers(img.device)
-        if self.stereo:
+        if self.sgbm is not None:
+            if right is None:
+                raise ValueError('the SGBM pipeline needs the right image')
+            disp_postp = self.disparity(img, right)
+            self.det.forward(img, disp_postp, b['head'])
+        elif self.stereo:
             if right is None:
                 raise ValueError('stereo pipeline needs the right image')
             disp_postp = self.disparity(img, right)
@@ -324,7 +346,7 @@ class InflightPipelines:
 
     def __getattr__(self, name):   # geometry / thresholds of the (identical) contexts: batch, max_det, stereo, ...
         if name in ('batch', 'max_det', 'stereo', 'height', 'width', 'ori_h', 'ori_w', 'agg_layers', 'agg3d_layers', 'split_bf16',
-                    'rgb_only', 'full_res'):
+                    'rgb_only', 'full_res', 'sgbm', 'takes_right'):
             return getattr(self.pipes[0], name)
         raise AttributeError(name)
 

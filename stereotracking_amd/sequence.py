@@ -284,9 +284,9 @@ def detect_shard(pipe, frames, device, check_overflow=True, uploader=None):
     B = one.batch
     bufs = []
     if uploader is None:
-        uploader = RawFrameUploader(B, (one.ori_h, one.ori_w), device, use_right=one.stereo)
+        uploader = RawFrameUploader(B, (one.ori_h, one.ori_w), device, use_right=one.takes_right)
     resident = isinstance(frames, HostSequence)
-    if not resident and not one.stereo and any(disparity_png_codes(f['disp']) is None for f in frames):
+    if not resident and not one.takes_right and any(disparity_png_codes(f['disp']) is None for f in frames):
         uploader = None        # disparity maps that no PNG could hold: fp32 upload (small tests only)
 
     def pack(out, n_real):
@@ -298,7 +298,7 @@ def detect_shard(pipe, frames, device, check_overflow=True, uploader=None):
             batch = uploader.upload((frames, i, i + n_real) if resident else frames[i:i + n_real])
         else:
             chunk = list(frames[i:i + n_real])
-            batch = frames_to_batch(chunk + [chunk[-1]] * (B - n_real), device, use_right=one.stereo)
+            batch = frames_to_batch(chunk + [chunk[-1]] * (B - n_real), device, use_right=one.takes_right)
         if runner is not None:   # packed under the context's stream, before that context is reused
             det, _ = runner.submit(batch['img'], right=batch.get('right'), disp_postp=batch.get('disp_postp'),
                                    post=lambda out, ctx, n=n_real: pack(out, n))
@@ -389,7 +389,7 @@ def run_video_replicas(pipe, videos, make_tracker, model, device, metrics=None, 
         frames = videos[name]
         one = pipe.pipes[0] if hasattr(pipe, 'submit') else pipe
         if uploader is None:
-            uploader = RawFrameUploader(one.batch, (one.ori_h, one.ori_w), device, use_right=one.stereo)
+            uploader = RawFrameUploader(one.batch, (one.ori_h, one.ori_w), device, use_right=one.takes_right)
         dets, counts = detect_shard(pipe, frames, device, uploader=uploader)
         tracks = track_gathered(dets, counts, len(frames), make_tracker(), model)   # frame_id 0 resets the tracker
         results[name] = tracks

@@ -1,0 +1,228 @@
+"""CPU: the StereoSGBM module's options and configuration, and known answers of the numpy restatement (tests/sgbm_ref.py)
+that tests/test_sgbm_gpu.py holds the HIP kernels to."""
+import os
+
+import numpy as np
+import pytest
+
+import sgbm_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CFG_DIR = os.path.join(ROOT, 'configs', 'stereo_tracking', 'ocsort')
+SECTION3 = dict(min_disparity=0, num_disparities=48, block_size=3, P1=96, P2=384, disp12_max_diff=0, uniqueness_ratio=10,
+                speckle_window_size=400, speckle_range=10, pre_filter_cap=63, mode='SGBM_3WAY', color=True)
+
+
+def _texture(h, w, seed=0, smooth=2):
+    rng = np.random.RandomState(seed)
+    t = rng.randint(0, 256, size=(3, h, w)).astype(np.float64)
+    if smooth > 1:
+        acc = np.zeros_like(t)
+        p = np.pad(t, ((0, 0), (smooth, smooth), (smooth, smooth)), mode='reflect')
+        for dy in range(smooth):
+            for dx in range(smooth):
+                acc += p[:, dy:dy + h, dx:dx + w]
+        t = acc / smooth ** 2
+    return np.clip(np.rint(t), 0, 255).astype(np.uint8)
+
+
+# ---- the module ---------------------------------------------------------------------------------------------------
+def test_models_builds_stereo_sgbm_with_section3_defaults():
+    from stereotracking_amd import mot  # noqa: F401  (registers the package's modules)
+    from stereotracking_amd.registry import MODELS
+    m = MODELS.build(dict(type='StereoSGBM'))
+    assert type(m).__name__ == 'StereoSGBM'
+    assert m.config() == SECTION3
+    assert list(m.parameters()) == [] and m.state_dict() == {}
+    with pytest.raises(RuntimeError, match='no CPU forward'):
+        m()
+
+
+def test_sgbm_config_parses_and_builds_the_shell():
+    from stereotracking_amd import mot  # noqa: F401
+    from stereotracking_amd.config import Config
+    from stereotracking_amd.registry import MODELS
+    cfg = Config.fromfile(os.path.join(CFG_DIR, 'stereo_yolox_s_mot_airdrone_sgbm.py'))
+    base = Config.fromfile(os.path.join(CFG_DIR, 'yolox_s_mmyolo_mot_airdrone_disp.py'))
+    assert cfg.model.stereo.type == 'StereoSGBM'
+    assert all(cfg.model.stereo[k] == v for k, v in SECTION3.items() if k != 'color')
+    model = MODELS.build(cfg.model)
+    assert type(model).__name__ == 'OCSORT_Disparity' and type(model.stereo).__name__ == 'StereoSGBM'
+    assert model.stereo.config() == SECTION3
+    assert model.detector.stereo is model.stereo
+    # everything else is the _disp config: the same detector / tracker settings
+    assert cfg.model.detector == base.model.detector and cfg.model.tracker == base.model.tracker
+    assert not any(k.startswith('stereo.') for k in model.state_dict())
+
+
+@pytest.mark.parametrize('kw,exc,match', [
+    (dict(mode='SGBM'), NotImplementedError, 'SGBM_3WAY'),
+    (dict(mode='HH'), NotImplementedError, 'SGBM_3WAY'),
+    (dict(min_disparity=4), NotImplementedError, 'min_disparity'),
+    (dict(num_disparities=96), ValueError, 'num_disparities'),
+    (dict(num_disparities=40), ValueError, 'num_disparities'),
+    (dict(block_size=4), ValueError, 'block_size'),
+    (dict(block_size=0), ValueError, 'block_size'),
+    (dict(block_size=5), ValueError, 'int16'),              # 3 (25 * 3 * 189 + 384) = 43677
+    (dict(P2=6000), ValueError, 'int16'),                   # 3 (9 * 3 * 189 + 6000) = 33309
+    (dict(pre_filter_cap=200), ValueError, 'pre_filter_cap'),
+    (dict(uniqueness_ratio=100), ValueError, 'uniqueness_ratio'),
+])
+def test_out_of_range_parameters_are_refused(kw, exc, match):
+    from stereotracking_amd.sgbm import StereoSGBM
+    with pytest.raises(exc, match=match):
+        StereoSGBM(**kw)
+
+
+def test_int16_bound_at_the_edge():
+    from stereotracking_amd.sgbm import StereoSGBM
+    # the shipped set: 3 * (9 * 3 * 189 + 384) = 16461
+    assert 3 * (9 * 3 * (2 * R.ftzero_of(63) + 63) + 384) == 16461
+    StereoSGBM(P2=32767 // 3 - 9 * 3 * 189)                  # = 10922 - 5103 = 5819: 32757 fits
+    with pytest.raises(ValueError, match='int16'):
+        StereoSGBM(P2=32767 // 3 - 9 * 3 * 189 + 4)          # 32769
+    StereoSGBM(block_size=7, color=False, P2=384)            # 3 (49 * 189 + 384) = 28935
+    with pytest.raises(ValueError, match='int16'):
+        StereoSGBM(block_size=9, color=False)                # 3 (81 * 189 + 384) = 47079
+    StereoSGBM(P1=400, P2=100)                               # P2' = P1 + 1 = 401: 3 (5103 + 401) = 16512
+
+
+def test_sgbm_mode_of_the_pipeline_needs_the_mono_plan():
+    from stereotracking_amd.pipeline import StereoDensePipeline
+    with pytest.raises(ValueError, match='stereo=False'):
+        StereoDensePipeline.__init__(object.__new__(StereoDensePipeline), 1, (64, 128), stereo=True,
+                                     sgbm=dict(type='StereoSGBM'))
+
+
+# ---- the restatement's known answers ----------------------------------------------------------------------------------
+def test_constant_image_has_no_disparity():
+    """A constant image: every level costs the same.  At the value ftzero (63) even the border columns (which hold
+    ftzero) agree, S is flat, and the uniqueness test invalidates every pixel.  At any other value the border column
+    w-1 prefers d = 0 by a margin that the right->left path carries along the whole row undiminished (it is <= P1), so
+    the rows decide d = 0.  Either way the map the detector sees is 0 everywhere."""
+    flat = np.full((3, 40, 96), 63, np.uint8)
+    st = R.sgbm(flat, flat, stages=True)
+    assert (st['raw'] == R.INVALID).all() and (st['final'] == R.INVALID).all()
+    other = np.full((3, 40, 96), 120, np.uint8)
+    st = R.sgbm(other, other, stages=True)
+    assert (st['raw'][:, :48] == R.INVALID).all() and (st['raw'][:, 48:] == 0).all()
+    for f in (R.sgbm(flat, flat), st['final']):
+        assert not R.disp_postp(f, 64, 96).any()
+
+
+def test_columns_left_of_D_are_zero():
+    from stereotracking_amd.synthetic import synthetic_stereo_pair
+    p = synthetic_stereo_pair(3, 64, 160, max_disp=48)
+    fin = R.sgbm(p['left'], p['right'])
+    assert (fin[:, :48] == R.INVALID).all()
+    out = R.disp_postp(fin, 96, 160)
+    assert (out[:, :, :48] == 0).all() and (out[:, 64:] == 0).all()
+    assert (out[0] == out[1]).all() and (out[0] == out[2]).all()
+
+
+@pytest.mark.parametrize('d0', [5, 17, 30])
+def test_textured_constant_shift(d0):
+    h, w = 48, 160
+    tex = _texture(h, w + d0, seed=d0)
+    left, right = tex[:, :, :w], tex[:, :, d0:d0 + w]       # right[x - d0] = left[x]
+    fin = R.sgbm(left, right)
+    inner = fin[4:-4, 56:-4]
+    assert (inner != R.INVALID).mean() > 0.95
+    v = inner[inner != R.INVALID]
+    assert np.abs(v / 16.0 - d0).max() <= 0.5
+
+
+def test_synthetic_pair_against_ground_truth():
+    """synthetic_stereo_pair(max_disp=48): of the pixels valid in both maps, >= 97 % are within 1 px of the truth (the
+    restatement's own run gives 98.8 % at 720 x 1280 and 98.9 % at this size, seed 0; occlusion edges and block borders
+    make up the rest)."""
+    from stereotracking_amd.synthetic import synthetic_stereo_pair
+    p = synthetic_stereo_pair(0, 160, 256, max_disp=48)
+    fin = R.sgbm(p['left'], p['right'])
+    gt = p['disp']
+    both = (fin > 0) & (gt > 0)
+    assert both.mean() > 0.5
+    assert (np.abs(fin[both] / 16.0 - gt[both]) <= 1).mean() >= 0.97
+
+
+def test_lr_check_removes_an_occluded_band():
+    """A foreground square at disparity 24 over a background at 8: the background band just left of the square is
+    visible in the left image only.  Without the LR check its pixels take a wrong level; with it they go."""
+    h, w, dfg, dbg = 48, 200, 24, 8
+    bg = _texture(h, w + 64, seed=1)
+    fg = _texture(h, w + 64, seed=2)
+    left = bg[:, :, :w].copy()
+    right = bg[:, :, dbg:dbg + w].copy()
+    x0, x1 = 110, 160
+    left[:, :, x0:x1] = fg[:, :, x0:x1]
+    right[:, :, x0 - dfg:x1 - dfg] = fg[:, :, x0:x1]
+    kw = dict(speckle_window_size=0, uniqueness_ratio=0)
+    no_lr = R.sgbm(left, right, stages=True, disp12_max_diff=1000, **kw)['raw']
+    lr = R.sgbm(left, right, stages=True, **kw)['raw']
+    band = slice(x0 - dfg + dbg + 2, x0 - 2)               # occluded in the right image
+    rows = slice(4, h - 4)
+    assert (no_lr[rows, band] != R.INVALID).mean() > 0.9
+    assert (lr[rows, band] == R.INVALID).mean() > 0.8
+    interior = lr[rows, x0 + 4:x1 - 4]
+    assert (np.abs(interior[interior != R.INVALID] / 16.0 - dfg) <= 1).all() and (interior != R.INVALID).mean() > 0.9
+
+
+def test_speckle_rule_at_400_and_401_pixels():
+    d = np.full((60, 80), R.INVALID, np.int64)
+    d[2:22, 2:22] = 320                                     # 400: removed
+    d[30:50, 2:22] = 320
+    d[50, 2] = 320                                          # 401: kept
+    out = R.speckles(d, 400, 160)
+    assert (out[2:22, 2:22] == R.INVALID).all()
+    assert (out[30:50, 2:22] == 320).all() and out[50, 2] == 320
+    assert (R.speckles(d, 0, 160) == d).all()              # speckle_window_size 0: no filter
+
+
+def test_speckle_chains_join_through_small_steps():
+    d = np.full((30, 80), R.INVALID, np.int64)
+    d[2:12, 0:50] = np.arange(50)[None] * 160 + 16          # 500 pixels in steps of exactly maxDiff: one component
+    d[15:25, 0:20] = 300
+    d[15:25, 20:40] = 461                                   # two 200-pixel blocks 161 apart: two small components
+    out = R.speckles(d, 400, 160)
+    assert (out[2:12, 0:50] == d[2:12, 0:50]).all()
+    assert (out[15:25, 0:40] == R.INVALID).all()
+    d[15:25, 20:40] = 460                                   # 160 apart: one 400-pixel component, still <= 400
+    assert (R.speckles(d, 400, 160)[15:25, 0:40] == R.INVALID).all()
+    assert (R.speckles(d, 399, 160)[15:25, 0:40] != R.INVALID).all()
+
+
+def test_subpixel_truncates_toward_zero():
+    # numerator (S[b-1] - S[b+1]) 16 + denom2 < 0: C division truncates toward zero, numpy's // would floor
+    assert R.trunc_div(np.array(-7), 4) == -1 and (-7) // 4 == -2
+    D = 16
+    S = np.full((1, 1, D), 1000, np.int64)
+    S[0, 0, 5], S[0, 0, 4], S[0, 0, 6] = 100, 130, 105      # denom2 = 35, num = 25 * 16 + 35 = 435 -> 435 // 70 = 6
+    S2 = S.copy()
+    S2[0, 0, 4], S2[0, 0, 6] = 105, 130                     # num = -25 * 16 + 35 = -365: trunc -5, floor -6
+    out = R.decide(S, D, D + 1, 10, 0)[0, D]
+    out2 = R.decide(S2, D, D + 1, 10, 0)[0, D]
+    assert out == 16 * 5 + 6 and out2 == 16 * 5 - 5
+
+
+def test_uniqueness_equality_and_ratio_zero():
+    D = 16
+    S = np.full((1, 1, D), 1000, np.int64)
+    S[0, 0, 3] = 90
+    S[0, 0, 10] = 100                                       # thresh = 9000 // 90 = 100: S <= thresh at |d - 3| > 1
+    assert R.decide(S, D, D + 1, 10, 0)[0, D] == R.INVALID
+    S[0, 0, 10] = 101
+    assert R.decide(S, D, D + 1, 10, 0)[0, D] != R.INVALID
+    S[0, 0, 10] = 90                                        # a tie far away: ratio 0 skips the test, lowest d wins
+    assert R.decide(S, D, D + 1, 10, 0)[0, D] == R.INVALID
+    assert R.decide(S, D, D + 1, 0, 0)[0, D] == 16 * 3
+
+
+def test_grey_mode_matches_on_the_bgr2gray_plane():
+    from stereotracking_amd.synthetic import synthetic_stereo_pair
+    p = synthetic_stereo_pair(5, 48, 128, max_disp=32)
+    g = R.sgbm(p['left'], p['right'], color=False, num_disparities=32)
+    gl, gr = R.to_grey(p['left']), R.to_grey(p['right'])
+    g3 = R.sgbm(np.repeat(gl, 3, 0).astype(np.uint8), np.repeat(gr, 3, 0).astype(np.uint8), color=False,
+                num_disparities=32)
+    assert np.array_equal(g, g3)                           # grey of a grey BGR image is the image itself
+    assert (g > 0).mean() > 0.3
