@@ -437,6 +437,29 @@ int st_box_depth(const float* disp_dev, size_t img_pitch, int N, int H, int W,
                  float focal, void* workspace_dev, size_t workspace_bytes, st_stream_t stream,
                  float* out_depth_dev, float* out_scale_dev, float* out_scaled_boxes_dev);
 
+/* Per-box depth estimators: the reference's default extract_depth and the four alternatives of its depth-extraction
+ * comparison (mmtrack/models/mot/depth_extraction_comparison.py).  All share the default's window, validity rule
+ * (0 < depth < 150) and discard rule (no valid depth or w > 800 => depth -1, scale 1); the alternatives scale by
+ * max(min(d * d / 400, 3), 1) (tests/depth_methods_ref.py):
+ *   TRUNCATED_MEAN  mean of sorted[int(0.1 n) : int(0.9 n)] (empty => sorted[:-1]; n == 1 => NaN)
+ *   MEAN            mean of the valid depths
+ *   MEDIAN          np.median of the valid depths
+ *   CENTER          raw depth[(y1 + y2) // 2, (x1 + x2) // 2] (numpy wrap; out of range => -1, scale 1) */
+enum {
+  ST_DEPTH_REFERENCE = 0,
+  ST_DEPTH_TRUNCATED_MEAN = 1,
+  ST_DEPTH_MEAN = 2,
+  ST_DEPTH_MEDIAN = 3,
+  ST_DEPTH_CENTER = 4
+};
+
+/* st_box_depth with the estimator `method` (ST_DEPTH_*; another value => ST_ERR_INVALID).  ST_DEPTH_REFERENCE launches
+ * exactly what st_box_depth launches.  Same grid (one workgroup per box), same outputs. */
+int st_box_depth_method(const float* disp_dev, size_t img_pitch, int N, int H, int W,
+                        const float* boxes_dev, const int32_t* counts_dev, int max_det, float baseline,
+                        float focal, void* workspace_dev, size_t workspace_bytes, st_stream_t stream,
+                        float* out_depth_dev, float* out_scale_dev, float* out_scaled_boxes_dev, int method);
+
 /* Frame records: the fixed-size, self-describing unit of the detection all-gather and of the ONE
  * device->host copy per chunk of the MOT shell: out (N, max_det + 1, cols) fp32, row 0 = [true count (may exceed
  * max_det = overflow), max_det, valid-frame flag, 0...], rows 1.. = x1,y1,x2,y2,score,label,depth,scale.

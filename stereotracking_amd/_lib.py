@@ -176,6 +176,7 @@ _PROTOS = {
     'st_box_depth_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'st_pack_records': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'st_box_depth': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp]),
+    'st_box_depth_method': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _i]),
 }
 
 _lib = None

@@ -23,6 +23,9 @@
 // once (numpy uses fp32 pairwise summation: equal to ~1e-6 relative, inside the 1e-3 float
 // tolerance of the path).  Windows of up to BD_CACHE pixels (every realistic drone box) are cached in
 // LDS by the counting pass, so the following passes never touch memory again.
+// st_box_depth_method adds the four estimators of the reference's depth-extraction comparison (truncated mean, mean,
+// median, centre pixel; scale d*d/400), each a template instance of the same kernel body: DESIGN.md section 11,
+// executable spec tests/depth_methods_ref.py.
 #include <algorithm>
 
 #include "st_common.h"
@@ -105,12 +108,14 @@ struct Window {
 // Precondition (set up by the kernel's counting pass, one barrier before the call): hist[0] = histogram of the TOP
 // byte of every valid depth - all ranks share the empty prefix, so the first radix pass needs no sweep of its own.
 // A pass is  count | barrier | prefix sums -> sh | barrier | use sh, re-zero the histograms | barrier.
+// BD_NR = 7 for the default estimator (median + 6 candidate bounds); the median / truncated-mean estimators select 2.
 constexpr int BD_NR = 7;
+template <int NR>
 __device__ void select_ranks(const Window& w, const int* ranks, unsigned (*hist)[256], unsigned* sh, unsigned* out) {
-  unsigned prefix[BD_NR], mask = 0;
-  int r[BD_NR];
+  unsigned prefix[NR], mask = 0;
+  int r[NR];
 #pragma unroll
-  for (int q = 0; q < BD_NR; ++q) { prefix[q] = 0; r[q] = ranks[q]; }
+  for (int q = 0; q < NR; ++q) { prefix[q] = 0; r[q] = ranks[q]; }
   for (int shift = 24; shift >= 0; shift -= 8) {
     unsigned (*hc)[256] = hist;
     if (shift != 24) {
@@ -118,7 +123,7 @@ __device__ void select_ranks(const Window& w, const int* ranks, unsigned (*hist)
         if (depth_valid(d)) {
           const unsigned u = __float_as_uint(d), um = u & mask, bin = (u >> shift) & 255u;
 #pragma unroll
-          for (int q = 0; q < BD_NR; ++q) {
+          for (int q = 0; q < NR; ++q) {
             // ranks that still share a prefix share a histogram: count once, in the first of them
             bool first = true;
 #pragma unroll
@@ -132,15 +137,15 @@ __device__ void select_ranks(const Window& w, const int* ranks, unsigned (*hist)
     // one wave per rank: 64-lane prefix sum over the 256 bins (4 bins per lane), the lane whose bins
     // straddle the rank reports (bin, count below it)
     const int wv0 = threadIdx.x >> 6, ln = threadIdx.x & 63, nwv = blockDim.x >> 6;
-    for (int wv = wv0; wv < BD_NR; wv += nwv) {   // the ranks are dealt over the waves of the workgroup
+    for (int wv = wv0; wv < NR; wv += nwv) {   // the ranks are dealt over the waves of the workgroup
       int rq = 0;
       unsigned pq = 0;
 #pragma unroll
-      for (int q = 0; q < BD_NR; ++q)
+      for (int q = 0; q < NR; ++q)
         if (q == wv) { rq = r[q]; pq = prefix[q]; }
       int src = wv;  // the histogram this rank's prefix was counted in
 #pragma unroll
-      for (int q2 = BD_NR - 1; q2 >= 0; --q2)
+      for (int q2 = NR - 1; q2 >= 0; --q2)
         if (q2 < wv && prefix[q2] == pq) src = q2;
       unsigned h[4];
 #pragma unroll
@@ -164,18 +169,18 @@ __device__ void select_ranks(const Window& w, const int* ranks, unsigned (*hist)
     }
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < BD_NR; ++q) {
+    for (int q = 0; q < NR; ++q) {
       prefix[q] |= sh[2 * q] << shift;
       r[q] -= (int)sh[2 * q + 1];
     }
     mask |= 255u << shift;
     if (shift != 0) {   // every reader of the histograms is behind the barrier above
-      for (int b = threadIdx.x; b < BD_NR * 256; b += blockDim.x) hist[b >> 8][b & 255] = 0;
+      for (int b = threadIdx.x; b < NR * 256; b += blockDim.x) hist[b >> 8][b & 255] = 0;
       __syncthreads();
     }
   }
 #pragma unroll
-  for (int q = 0; q < BD_NR; ++q) out[q] = prefix[q];
+  for (int q = 0; q < NR; ++q) out[q] = prefix[q];
 }
 
 __device__ float corner_mean(const float* disp, int H, int W, int r0, int r1, int c0, int c1, float bf,
@@ -193,15 +198,78 @@ __device__ float corner_mean(const float* disp, int H, int W, int r0, int r1, in
   return s / (float)cnt;
 }
 
-__global__ __launch_bounds__(BD_THREADS) void box_depth_kernel(const float* __restrict__ disp_all, size_t img_pitch, int H,
-                                                        int W, const float* __restrict__ boxes,
-                                                        const int* __restrict__ counts, int max_det, float bf,
-                                                        int is_depth, float* __restrict__ out_depth,
-                                                        float* __restrict__ out_scale,
-                                                        float* __restrict__ out_sboxes) {
+// trimmed mean of the sorted valid depths [a, b) (b > a) given the bit patterns of sorted[a] and sorted[b - 1]: one pass
+// sums the depths strictly between the two and counts those below / equal to each bound, so ties at a bound are
+// taken exactly as often as the slice holds them.  fp64 accumulation, rounded once.  All threads call it.
+__device__ __forceinline__ float trimmed_mean(const Window& w, int a, int b, unsigned va_bits, unsigned vb_bits,
+                                              double* s_red, int (*s_cnt)[BD_THREADS / 64]) {
+  const float va = __uint_as_float(va_bits), vb = __uint_as_float(vb_bits);
+  double sum = 0.0;
+  int lt_a = 0, eq_a = 0, lt_b = 0, eq_b = 0;
+  w.for_each([&](float d) {
+    if (depth_valid(d)) {
+      lt_a += d < va; eq_a += d == va;
+      lt_b += d < vb; eq_b += d == vb;
+      if (d > va && d < vb) sum += (double)d;
+    }
+  });
+  // wave reduction by shuffles, then one LDS slot per wave (fp64 sum: the order is fixed, so deterministic)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sum += __shfl_xor(sum, off);
+    lt_a += __shfl_xor(lt_a, off); eq_a += __shfl_xor(eq_a, off);
+    lt_b += __shfl_xor(lt_b, off); eq_b += __shfl_xor(eq_b, off);
+  }
+  const int wvr = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    s_red[wvr] = sum;
+    s_cnt[0][wvr] = lt_a; s_cnt[1][wvr] = eq_a; s_cnt[2][wvr] = lt_b; s_cnt[3][wvr] = eq_b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int v = 1; v < (int)(blockDim.x >> 6); ++v) {
+      s_red[0] += s_red[v];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) s_cnt[q][0] += s_cnt[q][v];
+    }
+  }
+  __syncthreads();
+  const int n_lt_a = s_cnt[0][0], n_eq_a = s_cnt[1][0], n_lt_b = s_cnt[2][0], n_eq_b = s_cnt[3][0];
+  double tot = s_red[0];
+  const int ca = min(n_lt_a + n_eq_a, b) - max(n_lt_a, a);
+  tot += (double)va * (double)ca;
+  if (vb_bits != va_bits) {
+    const int cb = min(n_lt_b + n_eq_b, b) - max(n_lt_b, a);
+    tot += (double)vb * (double)cb;
+  }
+  return (float)(tot / (double)(b - a));
+}
+
+// numpy floor division of two truncated box coordinates, then the index wrap of depth[cy, cx]: -1 when numpy would
+// raise IndexError (the CENTER estimator's stated deviation: such a box gets depth -1, scale 1)
+__device__ __forceinline__ int center_index(int lo, int hi, int len) {
+  const long long s = (long long)lo + hi;
+  long long c = s >= 0 ? s / 2 : -((-s + 1) / 2);
+  if (c < 0) c += len;
+  return (c < 0 || c >= len) ? -1 : (int)c;
+}
+
+// One workgroup per box.  METHOD (ST_DEPTH_*) is a template parameter: every estimator is its own instance, and the
+// default's instance is the kernel st_box_depth has always launched (box_depth_kernel below).
+//   REFERENCE       counting pass (LDS cache + top-byte histogram) -> 7-rank radix select -> trimmed mean
+//   TRUNCATED_MEAN  counting pass -> 2-rank select (the slice bounds) -> trimmed mean
+//   MEDIAN          counting pass -> 2-rank select ((n - 1) / 2, n / 2)
+//   MEAN            one pass: count + fp64 sum, no cache, no select
+//   CENTER          the centre pixel is loaded up front; the count stops at the first valid pixel (barrier-OR)
+template <int METHOD>
+__device__ __forceinline__ void box_depth_body(const float* __restrict__ disp_all, size_t img_pitch, int H, int W,
+                                               const float* __restrict__ boxes, const int* __restrict__ counts,
+                                               int max_det, float bf, int is_depth, float* __restrict__ out_depth,
+                                               float* __restrict__ out_scale, float* __restrict__ out_sboxes) {
+  constexpr int NR = METHOD == ST_DEPTH_REFERENCE ? BD_NR : 2;
   __shared__ float cache[BD_CACHE];
-  __shared__ unsigned hist[BD_NR][256];
-  __shared__ unsigned sh[2 * BD_NR];
+  __shared__ unsigned hist[NR][256];
+  __shared__ unsigned sh[2 * NR];
   __shared__ int s_len;
   __shared__ double s_red[BD_THREADS / 64];
   __shared__ int s_cnt[4][BD_THREADS / 64];
@@ -231,124 +299,177 @@ __global__ __launch_bounds__(BD_THREADS) void box_depth_kernel(const float* __re
   if ((x2 - x1) > 800) w.total = 0;  // the reference discards such boxes (`w > 800`): skip every pass
   const bool use_cache = w.total <= BD_CACHE;
   w.cache = nullptr;
-
-  // the 4 corner means only depend on the box: their (dependent, uncached) loads are issued here and land while the
-  // passes below run; they are compared with the median after the selection
-  const float v_tl = corner_mean(disp, H, W, y1, y1 + 2, x1, x1 + 2, bf, is_depth);
-  const float v_tr = corner_mean(disp, H, W, y1, y1 + 2, x2 - 2, x2, bf, is_depth);
-  const float v_bl = corner_mean(disp, H, W, y2 - 2, y2, x1, x1 + 2, bf, is_depth);
-  const float v_br = corner_mean(disp, H, W, y2 - 2, y2, x2 - 2, x2, bf, is_depth);
-
-  // ---- pass 0: number of valid depths, histogram of their top byte (= the first radix pass of select_ranks), and the
-  // LDS window cache
-  if (threadIdx.x == 0) s_len = 0;
-  for (int b = threadIdx.x; b < 256; b += blockDim.x) hist[0][b] = 0;
-  __syncthreads();
-  int local = 0;
-  auto tally = [&](float d) {
-    if (depth_valid(d)) {
-      ++local;
-      atomicAdd(&hist[0][__float_as_uint(d) >> 24], 1u);
-    }
-  };
-  if (use_cache) {
-    for (int e = threadIdx.x; e < w.total; e += blockDim.x) {
-      const float d = w.get(e);
-      cache[e] = d;
-      tally(d);
-    }
-  } else {
-    w.for_each(tally);
-  }
-  if (local) atomicAdd(&s_len, local);
-  __syncthreads();
-  if (use_cache) w.cache = cache;
-  const int len = s_len;
   float dval, scale;
-  if (len < 1 || (x2 - x1) > 800) {
-    dval = -1.0f;
+  [[maybe_unused]] bool has_d = false;   // the alternatives: a value was estimated, its scale is computed at the end
+
+  if constexpr (METHOD == ST_DEPTH_MEAN) {
+    int local = 0;
+    double sum = 0.0;
+    auto acc = [&](float d) {
+      if (depth_valid(d)) {
+        ++local;
+        sum += (double)d;
+      }
+    };
+    if (use_cache) {
+      for (int e = threadIdx.x; e < w.total; e += blockDim.x) acc(w.get(e));
+    } else {
+      w.for_each(acc);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      sum += __shfl_xor(sum, off);
+      local += __shfl_xor(local, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      s_red[threadIdx.x >> 6] = sum;
+      s_cnt[0][threadIdx.x >> 6] = local;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;   // thread 0 writes the outputs
+    int len = s_cnt[0][0];
+    sum = s_red[0];
+    for (int v = 1; v < (int)(blockDim.x >> 6); ++v) {
+      len += s_cnt[0][v];
+      sum += s_red[v];
+    }
+    has_d = len >= 1 && (x2 - x1) <= 800;
+    dval = has_d ? (float)(sum / (double)len) : -1.0f;
+    scale = 1.0f;
+  } else if constexpr (METHOD == ST_DEPTH_CENTER) {
+    // depth[cy, cx] of the RAW map, no validity filter; issued before the count so the load lands meanwhile
+    const int cy = center_index(y1, y2, H), cx = center_index(x1, x2, W);
+    const bool inside = cy >= 0 && cx >= 0;
+    const float vc = inside ? to_depth(disp[(size_t)cy * W + cx], bf, is_depth) : 0.f;
+    // len >= 1 is all the estimator needs: 4 pixels per lane per step, leave at the first step that saw a valid one
+    int found = 0;
+    for (int base = 0; base < w.total && !found; base += 4 * BD_THREADS) {
+      int any = 0;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int e = base + u * BD_THREADS + threadIdx.x;
+        if (e < w.total && depth_valid(w.get(e))) any = 1;
+      }
+      found = __syncthreads_or(any);
+    }
+    if (threadIdx.x != 0) return;
+    has_d = found && inside;   // found implies w <= 800 (the window is empty otherwise)
+    dval = has_d ? vc : -1.0f;
     scale = 1.0f;
   } else {
-    // the segment [a, b) depends on the median only through cnt in {0..4}, i.e. through 3 possible
-    // fractions (0.4, 0.25, 0): select the median and all 6 candidate bounds in the same 4 passes
-    int cand_a[3], cand_b[3];
-    const double fr[3] = {0.4, 0.25, 0.0};
+    // the 4 corner means only depend on the box: their (dependent, uncached) loads are issued here and land while the
+    // passes below run; they are compared with the median after the selection
+    float v_tl = 0.f, v_tr = 0.f, v_bl = 0.f, v_br = 0.f;
+    if constexpr (METHOD == ST_DEPTH_REFERENCE) {
+      v_tl = corner_mean(disp, H, W, y1, y1 + 2, x1, x1 + 2, bf, is_depth);
+      v_tr = corner_mean(disp, H, W, y1, y1 + 2, x2 - 2, x2, bf, is_depth);
+      v_bl = corner_mean(disp, H, W, y2 - 2, y2, x1, x1 + 2, bf, is_depth);
+      v_br = corner_mean(disp, H, W, y2 - 2, y2, x2 - 2, x2, bf, is_depth);
+    }
+
+    // ---- pass 0: number of valid depths, histogram of their top byte (= the first radix pass of select_ranks), and
+    // the LDS window cache
+    if (threadIdx.x == 0) s_len = 0;
+    for (int b = threadIdx.x; b < 256; b += blockDim.x) hist[0][b] = 0;
+    __syncthreads();
+    int local = 0;
+    auto tally = [&](float d) {
+      if (depth_valid(d)) {
+        ++local;
+        atomicAdd(&hist[0][__float_as_uint(d) >> 24], 1u);
+      }
+    };
+    if (use_cache) {
+      for (int e = threadIdx.x; e < w.total; e += blockDim.x) {
+        const float d = w.get(e);
+        cache[e] = d;
+        tally(d);
+      }
+    } else {
+      w.for_each(tally);
+    }
+    if (local) atomicAdd(&s_len, local);
+    __syncthreads();
+    if (use_cache) w.cache = cache;
+    const int len = s_len;
+    if (len < 1 || (x2 - x1) > 800) {
+      dval = -1.0f;
+      scale = 1.0f;
+    } else if constexpr (METHOD == ST_DEPTH_REFERENCE) {
+      // the segment [a, b) depends on the median only through cnt in {0..4}, i.e. through 3 possible
+      // fractions (0.4, 0.25, 0): select the median and all 6 candidate bounds in the same 4 passes
+      int cand_a[3], cand_b[3];
+      const double fr[3] = {0.4, 0.25, 0.0};
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double w_start = fr[c] * (double)len;
-      const double w_end = w_start + 0.6 * (double)len;
-      int a = (int)w_start, b = (int)w_end;
-      if (b > len) b = len;
-      if (a > len) a = len;
-      if (b - a <= 0) {  // d_seg empty -> d_sorted[:-1]
+      for (int c = 0; c < 3; ++c) {
+        const double w_start = fr[c] * (double)len;
+        const double w_end = w_start + 0.6 * (double)len;
+        int a = (int)w_start, b = (int)w_end;
+        if (b > len) b = len;
+        if (a > len) a = len;
+        if (b - a <= 0) {  // d_seg empty -> d_sorted[:-1]
+          a = 0;
+          b = len - 1;
+        }
+        cand_a[c] = a;
+        cand_b[c] = b;
+      }
+      int ranks[BD_NR];
+      unsigned bits[BD_NR];
+      ranks[0] = len / 2;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        ranks[1 + 2 * c] = min(cand_a[c], len - 1);
+        ranks[2 + 2 * c] = max(min(cand_b[c] - 1, len - 1), 0);
+      }
+      select_ranks<BD_NR>(w, ranks, hist, sh, bits);
+      const float d_mid = __uint_as_float(bits[0]);
+      const int cnt = (v_tl > d_mid) + (v_tr > d_mid) + (v_bl > d_mid) + (v_br > d_mid);
+      // frac = min(1 - cnt/4, 0.4): cnt <= 2 -> 0.4, cnt == 3 -> 0.25, cnt == 4 -> 0
+      const int csel = cnt <= 2 ? 0 : (cnt == 3 ? 1 : 2);
+      const int a = cand_a[csel], b = cand_b[csel];
+      if (b - a <= 0) {
+        dval = __builtin_nanf("");
+      } else {
+        dval = trimmed_mean(w, a, b, bits[1 + 2 * csel], bits[2 + 2 * csel], s_red, s_cnt);
+      }
+      const float dd = dval * dval;
+      scale = (3.0f < dd) ? 3.0f : dd;       // Python min(dd, 3.): NaN stays
+      scale = (1.0f > scale) ? 1.0f : scale;  // Python max(scale, 1.)
+    } else if constexpr (METHOD == ST_DEPTH_TRUNCATED_MEAN) {
+      // sorted[int(0.1 n) : int((1 - 0.1) n)] (Python doubles), empty -> sorted[:-1], still empty (n == 1) -> NaN
+      int a = (int)(0.1 * (double)len), b = (int)((1.0 - 0.1) * (double)len);
+      if (b - a <= 0) {
         a = 0;
         b = len - 1;
       }
-      cand_a[c] = a;
-      cand_b[c] = b;
+      if (b - a <= 0) {
+        dval = __builtin_nanf("");
+      } else {
+        const int ranks[2] = {a, b - 1};
+        unsigned bits[2];
+        select_ranks<2>(w, ranks, hist, sh, bits);
+        dval = trimmed_mean(w, a, b, bits[0], bits[1], s_red, s_cnt);
+      }
+      has_d = true;
+    } else {  // MEDIAN: np.median - the middle element, or the fp32 sum of the two middle ones halved
+      const int ranks[2] = {(len - 1) / 2, len / 2};
+      unsigned bits[2];
+      select_ranks<2>(w, ranks, hist, sh, bits);
+      const float lo = __uint_as_float(bits[0]), hi = __uint_as_float(bits[1]);
+      dval = (len & 1) ? hi : (lo + hi) / 2.0f;
+      has_d = true;
     }
-    int ranks[BD_NR];
-    unsigned bits[BD_NR];
-    ranks[0] = len / 2;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      ranks[1 + 2 * c] = min(cand_a[c], len - 1);
-      ranks[2 + 2 * c] = max(min(cand_b[c] - 1, len - 1), 0);
+  }
+  if constexpr (METHOD != ST_DEPTH_REFERENCE) {
+    // the alternatives' scale: max(min(d * d / 400, 3.), 1.) - d * d is a float32 scalar product, / 400 promotes to a
+    // Python float (numpy < 1.24 scalar rules), min / max let NaN through; the list becomes a float32 tensor
+    if (has_d) {
+      double s = (double)(dval * dval) / 400.0;
+      s = (3.0 < s) ? 3.0 : s;
+      s = (1.0 > s) ? 1.0 : s;
+      scale = (float)s;
     }
-    select_ranks(w, ranks, hist, sh, bits);
-    const float d_mid = __uint_as_float(bits[0]);
-    const int cnt = (v_tl > d_mid) + (v_tr > d_mid) + (v_bl > d_mid) + (v_br > d_mid);
-    // frac = min(1 - cnt/4, 0.4): cnt <= 2 -> 0.4, cnt == 3 -> 0.25, cnt == 4 -> 0
-    const int csel = cnt <= 2 ? 0 : (cnt == 3 ? 1 : 2);
-    const int a = cand_a[csel], b = cand_b[csel];
-    if (b - a <= 0) {
-      dval = __builtin_nanf("");
-    } else {
-      const unsigned va_bits = bits[1 + 2 * csel], vb_bits = bits[2 + 2 * csel];
-      const float va = __uint_as_float(va_bits), vb = __uint_as_float(vb_bits);
-      double sum = 0.0;
-      int lt_a = 0, eq_a = 0, lt_b = 0, eq_b = 0;
-      w.for_each([&](float d) {
-        if (depth_valid(d)) {
-          lt_a += d < va; eq_a += d == va;
-          lt_b += d < vb; eq_b += d == vb;
-          if (d > va && d < vb) sum += (double)d;
-        }
-      });
-      // wave reduction by shuffles, then one LDS slot per wave (fp64 sum: the order is fixed, so deterministic)
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        sum += __shfl_xor(sum, off);
-        lt_a += __shfl_xor(lt_a, off); eq_a += __shfl_xor(eq_a, off);
-        lt_b += __shfl_xor(lt_b, off); eq_b += __shfl_xor(eq_b, off);
-      }
-      const int wvr = threadIdx.x >> 6;
-      if ((threadIdx.x & 63) == 0) {
-        s_red[wvr] = sum;
-        s_cnt[0][wvr] = lt_a; s_cnt[1][wvr] = eq_a; s_cnt[2][wvr] = lt_b; s_cnt[3][wvr] = eq_b;
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        for (int v = 1; v < (int)(blockDim.x >> 6); ++v) {
-          s_red[0] += s_red[v];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) s_cnt[q][0] += s_cnt[q][v];
-        }
-      }
-      __syncthreads();
-      const int n_lt_a = s_cnt[0][0], n_eq_a = s_cnt[1][0], n_lt_b = s_cnt[2][0], n_eq_b = s_cnt[3][0];
-      double tot = s_red[0];
-      const int ca = min(n_lt_a + n_eq_a, b) - max(n_lt_a, a);
-      tot += (double)va * (double)ca;
-      if (vb_bits != va_bits) {
-        const int cb = min(n_lt_b + n_eq_b, b) - max(n_lt_b, a);
-        tot += (double)vb * (double)cb;
-      }
-      dval = (float)(tot / (double)(b - a));
-    }
-    const float dd = dval * dval;
-    scale = (3.0f < dd) ? 3.0f : dd;       // Python min(dd, 3.): NaN stays
-    scale = (1.0f > scale) ? 1.0f : scale;  // Python max(scale, 1.)
   }
   if (threadIdx.x == 0) {
     const size_t o = (size_t)n * max_det + k;
@@ -360,6 +481,22 @@ __global__ __launch_bounds__(BD_THREADS) void box_depth_kernel(const float* __re
     f32x4 ob = {cx - bw / 2.0f, cy - bh / 2.0f, cx + bw / 2.0f, cy + bh / 2.0f};
     *reinterpret_cast<f32x4*>(out_sboxes + o * 4) = ob;
   }
+}
+
+#define BD_ARGS                                                                                                      \
+  const float *__restrict__ disp_all, size_t img_pitch, int H, int W, const float *__restrict__ boxes,               \
+      const int *__restrict__ counts, int max_det, float bf, int is_depth, float *__restrict__ out_depth,            \
+      float *__restrict__ out_scale, float *__restrict__ out_sboxes
+#define BD_PASS disp_all, img_pitch, H, W, boxes, counts, max_det, bf, is_depth, out_depth, out_scale, out_sboxes
+
+// the default estimator keeps its kernel (name, launch, code) unchanged; the alternatives are instances of their own
+__global__ __launch_bounds__(BD_THREADS) void box_depth_kernel(BD_ARGS) {
+  box_depth_body<ST_DEPTH_REFERENCE>(BD_PASS);
+}
+
+template <int METHOD>
+__global__ __launch_bounds__(BD_THREADS) void box_depth_method_kernel(BD_ARGS) {
+  box_depth_body<METHOD>(BD_PASS);
 }
 
 // Frame records for the all-gather / the one D2H copy per chunk: (N, M + 1, cols) fp32.  Row 0 = header [true count,
@@ -426,22 +563,53 @@ extern "C" int st_pack_records(const float* boxes_dev, const float* scores_dev, 
 
 extern "C" size_t st_box_depth_workspace_bytes(int, int, int, int) { return 0; }
 
-extern "C" int st_box_depth(const float* disp_dev, size_t img_pitch, int N, int H, int W, const float* boxes_dev,
-                            const int32_t* counts_dev, int max_det, float baseline, float focal, void*, size_t,
-                            st_stream_t stream_, float* out_depth_dev, float* out_scale_dev,
-                            float* out_scaled_boxes_dev) {
+namespace {
+
+int box_depth_launch(const float* disp_dev, size_t img_pitch, int N, int H, int W, const float* boxes_dev,
+                     const int32_t* counts_dev, int max_det, float baseline, float focal, st_stream_t stream_,
+                     float* out_depth_dev, float* out_scale_dev, float* out_scaled_boxes_dev, int method) {
   using namespace st;
   ST_REQUIRE(disp_dev && boxes_dev && counts_dev && out_depth_dev && out_scale_dev && out_scaled_boxes_dev,
              "st_box_depth: null pointer");
   ST_REQUIRE(N > 0 && H > 0 && W > 0 && max_det > 0 && N <= 65535, "st_box_depth: bad geometry");
   ST_REQUIRE(img_pitch >= (size_t)H * W, "st_box_depth: img_pitch smaller than one image");
+  ST_REQUIRE(method >= ST_DEPTH_REFERENCE && method <= ST_DEPTH_CENTER, "st_box_depth_method: unknown method %d",
+             method);
   // baseline < 0 selects "input is already a depth map" (reference passes gt depth_postp that way,
   // ocsort_disparity.py:120-122); bf = baseline * focal as a Python float product rounded to fp32
   const int is_depth = baseline < 0.f;
   const float bf = (float)((double)baseline * (double)focal);
-  hipLaunchKernelGGL(box_depth_kernel, dim3(max_det, N), dim3(BD_THREADS), 0, static_cast<hipStream_t>(stream_), disp_dev,
-                     img_pitch, H, W, boxes_dev, counts_dev, max_det, bf, is_depth, out_depth_dev, out_scale_dev,
-                     out_scaled_boxes_dev);
+  const hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const dim3 grid(max_det, N), block(BD_THREADS);
+#define BD_LAUNCH(kernel)                                                                                           \
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, disp_dev, img_pitch, H, W, boxes_dev, counts_dev, max_det, bf, \
+                     is_depth, out_depth_dev, out_scale_dev, out_scaled_boxes_dev)
+  switch (method) {
+    case ST_DEPTH_REFERENCE: BD_LAUNCH(box_depth_kernel); break;
+    case ST_DEPTH_TRUNCATED_MEAN: BD_LAUNCH(box_depth_method_kernel<ST_DEPTH_TRUNCATED_MEAN>); break;
+    case ST_DEPTH_MEAN: BD_LAUNCH(box_depth_method_kernel<ST_DEPTH_MEAN>); break;
+    case ST_DEPTH_MEDIAN: BD_LAUNCH(box_depth_method_kernel<ST_DEPTH_MEDIAN>); break;
+    default: BD_LAUNCH(box_depth_method_kernel<ST_DEPTH_CENTER>); break;
+  }
+#undef BD_LAUNCH
   ST_CHECK_HIP(hipGetLastError());
   return ST_OK;
+}
+
+}  // namespace
+
+extern "C" int st_box_depth(const float* disp_dev, size_t img_pitch, int N, int H, int W, const float* boxes_dev,
+                            const int32_t* counts_dev, int max_det, float baseline, float focal, void*, size_t,
+                            st_stream_t stream_, float* out_depth_dev, float* out_scale_dev,
+                            float* out_scaled_boxes_dev) {
+  return box_depth_launch(disp_dev, img_pitch, N, H, W, boxes_dev, counts_dev, max_det, baseline, focal, stream_,
+                          out_depth_dev, out_scale_dev, out_scaled_boxes_dev, ST_DEPTH_REFERENCE);
+}
+
+extern "C" int st_box_depth_method(const float* disp_dev, size_t img_pitch, int N, int H, int W,
+                                   const float* boxes_dev, const int32_t* counts_dev, int max_det, float baseline,
+                                   float focal, void*, size_t, st_stream_t stream_, float* out_depth_dev,
+                                   float* out_scale_dev, float* out_scaled_boxes_dev, int method) {
+  return box_depth_launch(disp_dev, img_pitch, N, H, W, boxes_dev, counts_dev, max_det, baseline, focal, stream_,
+                          out_depth_dev, out_scale_dev, out_scaled_boxes_dev, method);
 }

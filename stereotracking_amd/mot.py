@@ -9,6 +9,9 @@ The dense work (detector, decode+NMS, per-box depth) is enqueued on the GPU thro
 association step runs on the CPU (stereotracking_amd/trackers.py), as north_star prescribes.
 Relaxation of the reference: `predict` accepts N >= 1 frames of ONE video in frame
 order — the dense path runs batched, the tracker consumes the frames sequentially.
+Per-box depth: OCSORT_Disparity(depth_extraction=...) picks the estimator of every depth call, 'reference' (the
+reference's default extract_depth) or one of its depth-extraction comparison, 'truncated_mean', 'mean', 'median' or
+'center' (DESIGN.md §11).
 """
 import ctypes as C
 
@@ -291,13 +294,19 @@ class OCSORT_Disparity(nn.Module):
     StereoSGBM the mono detector runs on the SGBM disparity of the left / right frames), `dense_batch`,
     `inflight`, `max_det` (rows of the detection buffer: a capacity, overflow raises) and `results_device`
     ('cpu': results stay where the CPU tracker produced them - the consumers are the host-side evaluator / CSV
-    writer; 'input': moved back to the device of the inputs like the reference's tensors)."""
+    writer; 'input': moved back to the device of the inputs like the reference's tensors) and `depth_extraction`
+    (the per-box depth estimator of the detections, the track boxes and the gt depth alike: 'reference', or
+    'truncated_mean' / 'mean' / 'median' / 'center', the alternatives the reference selects by decorating
+    extract_depth, mmtrack/models/mot/depth_extraction_comparison.py)."""
 
     def __init__(self, detector=None, tracker=None, motion=None, data_preprocessor=None, init_cfg=None,
                  baseline=0.25, focal_length=640, stereo=None, dense_batch=8, inflight=3, max_det=1000,
                  results_device='cpu', autotune=True, tuning_cache=None, results_csv=None, split_bf16=None,
-                 queue_depth=1):
+                 queue_depth=1, depth_extraction='reference'):
         super().__init__()
+        from .pipeline import depth_method_code
+        depth_method_code(depth_extraction)     # ValueError for an unknown estimator, before anything is built
+        self.depth_extraction = depth_extraction
         self.data_preprocessor = MODELS.build(data_preprocessor) if data_preprocessor is not None else None
         self.detector = MODELS.build(detector) if detector is not None else None
         self.motion = TASK_UTILS.build(motion) if motion is not None else None
@@ -337,7 +346,7 @@ class OCSORT_Disparity(nn.Module):
             except (TypeError, ValueError):
                 self._pre_lazy = False
         self.lib = _lib.load()
-        self._dense = {}          # (batch, ori_h, ori_w, stereo) -> [InflightPipelines, weights version]
+        self._dense = {}          # (batch, ori_h, ori_w, stereo, depth_extraction) -> [InflightPipelines, weights version]
         self._staging = {}        # name -> pinned host buffer (grow-only): no pinned allocation on the per-chunk path
         self.timings = dict(frames=0, tracker_s=0.0, host_s=0.0, wait_s=0.0, pre_s=0.0, tail_s=0.0, submit_s=0.0, depth_s=0.0)   # cumulative host-side costs
 
@@ -380,7 +389,7 @@ class OCSORT_Disparity(nn.Module):
             raise NotImplementedError('the batched dense path implements the shipped yolox_style=True post-processing '
                                       '(no max_per_img cut); use detector.predict for other test_cfg')
         batch = int(batch or self.dense_batch)
-        key = (batch, int(ori_hw[0]), int(ori_hw[1]), bool(stereo))
+        key = (batch, int(ori_hw[0]), int(ori_hw[1]), bool(stereo), self.depth_extraction)
         ent = self._dense.get(key)
         if ent is None:
             sm = self.stereo
@@ -399,7 +408,7 @@ class OCSORT_Disparity(nn.Module):
                 rgb_only=getattr(det, 'rgb_only', False),
                 full_res=bool(getattr(sm, 'full_res', False)) if stereo else False,
                 full_res_channels=(sm.reduce.out_channels if stereo and getattr(sm, 'full_res', False) else 8),
-                sgbm=sgbm)
+                sgbm=sgbm, depth_method=self.depth_extraction)
             for p in runner.pipes:     # the track-box depth reads run k's disparity while later runs are in flight
                 p.disp_buffers = self.queue_depth + 1
             ent = self._dense[key] = [runner, None]
@@ -446,7 +455,10 @@ class OCSORT_Disparity(nn.Module):
 
     def _box_depth(self, disp, boxes, counts, baseline, focal):
         """ONE st_box_depth launch for a whole batch: disp (N,C,H,W), boxes (N,M,4), counts (N,) int32 or None
-        (= all M rows) -> depth (N,M), scales (N,M), scaled boxes (N,M,4)."""
+        (= all M rows) -> depth (N,M), scales (N,M), scaled boxes (N,M,4).  The estimator is `depth_extraction`
+        (st_box_depth_method for the alternatives)."""
+        from .pipeline import depth_method_code
+        method = depth_method_code(self.depth_extraction)
         N, M = boxes.shape[0], boxes.shape[1]
         dev = boxes.device
         if M == 0:
@@ -458,9 +470,13 @@ class OCSORT_Disparity(nn.Module):
         disp = disp.float().contiguous()
         if counts is None:
             counts = torch.full((N,), M, dtype=torch.int32, device=dev)
-        check(self.lib.st_box_depth(ptr(disp), Cc * H * W, N, H, W, ptr(boxes.float().contiguous()), ptr(counts), M,
-                                    float(baseline), float(focal), None, 0, current_stream(), ptr(depth), ptr(scales),
-                                    ptr(sboxes)), 'st_box_depth')
+        boxes = boxes.float().contiguous()
+        args = (ptr(disp), Cc * H * W, N, H, W, ptr(boxes), ptr(counts), M, float(baseline),
+                float(focal), None, 0, current_stream(), ptr(depth), ptr(scales), ptr(sboxes))
+        if method == 0:
+            check(self.lib.st_box_depth(*args), 'st_box_depth')
+        else:
+            check(self.lib.st_box_depth_method(*args, method), 'st_box_depth_method')
         return depth, scales, sboxes
 
     # ---- predict (ocsort_disparity.py:50-111) ------------------------------------------------------------

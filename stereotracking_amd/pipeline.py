@@ -19,6 +19,18 @@ from .engine import HipDetector, RawChunk, _require_cuda
 from .stereo import StereoCostVolume
 
 
+# per-box depth estimators (include/stereotrack.h ST_DEPTH_*): the reference's default extract_depth and the four
+# alternatives of its depth-extraction comparison (mmtrack/models/mot/depth_extraction_comparison.py)
+DEPTH_METHODS = {'reference': 0, 'truncated_mean': 1, 'mean': 2, 'median': 3, 'center': 4}
+
+
+def depth_method_code(name):
+    """ST_DEPTH_* code of a depth_method / depth_extraction name; ValueError for anything else."""
+    if not isinstance(name, str) or name not in DEPTH_METHODS:
+        raise ValueError(f'unknown depth extraction method {name!r}: one of {", ".join(DEPTH_METHODS)}')
+    return DEPTH_METHODS[name]
+
+
 def committed_tuning_plans():
     """configs/tuning/mi355x.json: the plans committed with the repository.  READ-ONLY for the package - one committed
     plan per graph makes the kernel instances (and with them the fp32 summation order, i.e. every float the path
@@ -93,7 +105,8 @@ class StereoDensePipeline:
     def __init__(self, batch, ori_shape=(720, 1280), widen_factor=0.5, deepen_factor=0.33, num_classes=1,
                  stereo=True, max_disp=192, feat_stride=4, temperature=32.0, score_thr=0.01, iou_thr=0.5,
                  max_det=1000, baseline=0.25, focal_length=640, pad_size_divisor=32, agg_layers=0, agg3d_layers=0,
-                 split_bf16=None, multi_label=True, rgb_only=False, full_res=False, full_res_channels=8, sgbm=None):
+                 split_bf16=None, multi_label=True, rgb_only=False, full_res=False, full_res_channels=8, sgbm=None,
+                 depth_method='reference'):
         """max_det: rows of the fixed-size detection buffer per frame.  The reference applies NO cap on the
         kept boxes (yolox_style=True => max_per_img = len(results)), so this is a
         capacity, not a threshold: `run()` reports `overflow` whenever a frame kept more boxes than fit, and
@@ -102,7 +115,12 @@ class StereoDensePipeline:
         sgbm: a StereoSGBM config dict (or module, whose configuration is copied: every context owns its workspace).
         The pipeline then takes left + right frames like the stereo mode, computes the disparity with OpenCV's
         SGBM_3WAY restated on the device (sgbm.py) into the same disp_postp ring, and runs the MONO detector plan
-        (stereo must be False) on img + that disparity - the configuration the reference's detector was trained in."""
+        (stereo must be False) on img + that disparity - the configuration the reference's detector was trained in.
+
+        depth_method: the per-box depth estimator of box_depth() (DEPTH_METHODS; 'reference' = the reference's default
+        extract_depth, launched through st_box_depth exactly as before)."""
+        self.depth_method = str(depth_method)
+        self._depth_code = depth_method_code(depth_method)
         self.lib = _lib.load()
         self.batch = int(batch)
         self.ori_h, self.ori_w = int(ori_shape[0]), int(ori_shape[1])
@@ -263,9 +281,12 @@ class StereoDensePipeline:
         b = self._buffers(disp_postp.device)
         N, M = boxes.shape[0], boxes.shape[1]
         depth, scales, sboxes = out if out is not None else (b['depth'], b['scales'], b['scaled_boxes'])
-        check(self.lib.st_box_depth(ptr(disp_postp), 3 * self.height * self.width, N, self.height, self.width,
-                                    ptr(boxes), ptr(counts), M, self.baseline, self.focal_length, None, 0,
-                                    current_stream(), ptr(depth), ptr(scales), ptr(sboxes)), 'st_box_depth')
+        args = (ptr(disp_postp), 3 * self.height * self.width, N, self.height, self.width, ptr(boxes), ptr(counts), M,
+                self.baseline, self.focal_length, None, 0, current_stream(), ptr(depth), ptr(scales), ptr(sboxes))
+        if self._depth_code == 0:
+            check(self.lib.st_box_depth(*args), 'st_box_depth')
+        else:
+            check(self.lib.st_box_depth_method(*args, self._depth_code), 'st_box_depth_method')
         return depth, scales, sboxes
 
     def run(self, img, right=None, disp_postp=None):
@@ -346,7 +367,7 @@ class InflightPipelines:
 
     def __getattr__(self, name):   # geometry / thresholds of the (identical) contexts: batch, max_det, stereo, ...
         if name in ('batch', 'max_det', 'stereo', 'height', 'width', 'ori_h', 'ori_w', 'agg_layers', 'agg3d_layers', 'split_bf16',
-                    'rgb_only', 'full_res', 'sgbm', 'takes_right'):
+                    'rgb_only', 'full_res', 'sgbm', 'takes_right', 'depth_method'):
             return getattr(self.pipes[0], name)
         raise AttributeError(name)
 

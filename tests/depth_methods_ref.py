@@ -1,0 +1,115 @@
+"""Executable spec of the four alternative per-box depth estimators (csrc/box_depth.hip, st_box_depth_method): the
+reference's depth-extraction comparison (mmtrack/models/mot/depth_extraction_comparison.py: truncated_mean_decorator,
+mean_decorator, median_decorator, center_decorator), restated in numpy from the rules below.  DESIGN.md section 11.
+
+Front end, shared with the default extract_depth (oracle/depth.py):
+  R1  depth map: disparity input -> depth = float32(baseline * focal) / (disp + float32(1e-6)), fp32 IEEE divide;
+      gt-depth input (baseline < 0 at the ABI) -> the raw map as given.  Channel 0 of (C, H, W), H x W = the padded
+      map the model holds.
+  R2  box.astype(np.int): every coordinate truncated toward zero.
+  R3  window = depth[y1:y2, x1:x2] with Python slice rules (negative indices wrap once, out of range clamps, start >=
+      stop is empty).
+  R4  valid pixels v = window[(window < 150) & (window > 0)], n = len(v), s = sort(v).
+  R5  n < 1 or (x2 - x1) > 800 -> depth -1, scale 1.0.
+Values (n >= 1 and w <= 800):
+  R6  truncated_mean: s[int(0.1 n) : int((1 - 0.1) n)] with the bounds computed in doubles; if that is empty,
+      s[:-1]; its mean.  Only n == 1 is still empty after the fallback: NaN (np.mean of an empty slice).
+  R7  mean: mean(v).
+  R8  median: np.median(v) = s[n // 2] for odd n; for even n (s[n/2 - 1] + s[n/2]) added in fp32, then halved.
+  R9  center: depth[cy, cx] of the RAW map (no validity filter), cx = (x1 + x2) // 2, cy = (y1 + y2) // 2 (floor
+      division of the truncated ints); a negative index wraps once as in numpy.  Still gated by R5.
+  R10 (stated deviation) center index out of range after the wrap: numpy raises IndexError; here depth -1, scale 1.0.
+      Unscaled Kalman track boxes can reach past the map.
+  R11 means (R6, R7) are accumulated in float64 and rounded to float32 once.  numpy sums float32 pairwise in
+      float32; the device accumulates in float64 too, and may differ from this restatement by 1 fp32 ulp (the order
+      of the float64 sum).
+Scale:
+  R12 scale = max(min(d * d / 400, 3.), 1.) with Python's min / max: NaN passes through both.
+  R13 (uncertain) numpy promotion: the reference pins numpy < 1.24, where d is an np.float32 scalar, d * d an
+      np.float32 product, and `/ 400` (all-scalar operands, Python int) promotes to float64.  So: float32 product,
+      float64 quotient, float64 clamps, float32 when the list becomes a tensor.  NumPy >= 2 (NEP 50) would keep
+      float32 for the quotient; this restatement spells the legacy reading out and does not depend on the
+      installed numpy.
+"""
+import numpy as np
+
+METHODS = ('truncated_mean', 'mean', 'median', 'center')
+MAX_DEPTH = 150
+MAX_WIDTH = 800
+
+
+def depth_map(disp, baseline=0.25, focal=640.0, is_depth=False):
+    """R1: (H, W) float32 depth of a disparity map (or the gt-depth map itself)."""
+    d = np.asarray(disp, np.float32)
+    if is_depth:
+        return d
+    bf = np.float32(float(baseline) * float(focal))
+    return (bf / (d + np.float32(1e-6))).astype(np.float32)
+
+
+def _mean64(a):
+    """R11: float64 accumulation, one rounding."""
+    return np.float32(np.sum(a, dtype=np.float64) / len(a))
+
+
+def value(depth, box, method):
+    """R2-R10 for one box -> (float32 depth value, estimated?)  estimated False = the (-1, 1.0) row."""
+    H, W = depth.shape
+    x1, y1, x2, y2 = (int(c) for c in np.asarray(box, np.float32))          # R2: int() truncates toward zero
+    win = depth[y1:y2, x1:x2]                                                 # R3
+    v = win[(win < MAX_DEPTH) & (win > 0)]                                    # R4
+    n = len(v)
+    if n < 1 or (x2 - x1) > MAX_WIDTH:                                        # R5
+        return np.float32(-1.0), False
+    if method == 'center':                                                    # R9
+        cx, cy = (x1 + x2) // 2, (y1 + y2) // 2
+        cx, cy = cx + W if cx < 0 else cx, cy + H if cy < 0 else cy
+        if not (0 <= cx < W and 0 <= cy < H):                                 # R10
+            return np.float32(-1.0), False
+        return np.float32(depth[cy, cx]), True
+    if method == 'mean':                                                      # R7
+        return _mean64(v), True
+    s = np.sort(v)
+    if method == 'median':                                                    # R8
+        if n % 2:
+            return np.float32(s[n // 2]), True
+        return np.float32(np.float32(s[n // 2 - 1]) + np.float32(s[n // 2])) / np.float32(2), True
+    if method == 'truncated_mean':                                            # R6
+        seg = s[int(0.1 * n):int((1 - 0.1) * n)]
+        if len(seg) == 0:
+            seg = s[:-1]
+        if len(seg) == 0:
+            return np.float32(np.nan), True
+        return _mean64(seg), True
+    raise ValueError(f'unknown method {method!r}')
+
+
+def scale_of(d):
+    """R12-R13: float32 product, float64 quotient and clamps (Python min / max), float32 result."""
+    d = np.float32(d)
+    with np.errstate(over='ignore', invalid='ignore'):
+        dd = np.float32(d * d)
+    s = float(dd) / 400.0
+    s = min(s, 3.)
+    s = max(s, 1.)
+    return np.float32(s)
+
+
+def extract_depth(depth, boxes, method):
+    """(H, W) float32 depth map, (M, 4) boxes -> depth values (M,) float32, scales (M,) float32."""
+    vals, scales = [], []
+    for box in np.asarray(boxes, np.float32).reshape(-1, 4):
+        d, ok = value(depth, box, method)
+        vals.append(d)
+        scales.append(scale_of(d) if ok else np.float32(1.0))
+    return np.asarray(vals, np.float32), np.asarray(scales, np.float32)
+
+
+def scale_bbox(boxes, scales):
+    """trackers/utils.py:58-73 in float32 (what the kernel writes as the scaled boxes)."""
+    b = np.asarray(boxes, np.float32).reshape(-1, 4)
+    sc = np.asarray(scales, np.float32)
+    two = np.float32(2.0)
+    cx, cy = (b[:, 0] + b[:, 2]) / two, (b[:, 1] + b[:, 3]) / two
+    w, h = (b[:, 2] - b[:, 0]) * sc, (b[:, 3] - b[:, 1]) * sc
+    return np.stack([cx - w / two, cy - h / two, cx + w / two, cy + h / two], axis=1).astype(np.float32)
