@@ -25,6 +25,11 @@ ships no fixtures of its own, so these vectors pin the oracle, not the reference
   shell_sequence.npz   the 6-frame 80x160 scenario of tests/test_shell_gpu.py (disparity given as input, tiny detector):
                        oracle detector -> C decode+NMS -> numpy extract_depth -> ORACLE tracker; kept priors, track ids
                        and unscaled track boxes per frame
+  tracker_options.npz  six 48-step detection streams (occlusion + duplicates; NaN rows as extract_depth emits them;
+                       the area-100 boundary, zero-width boxes, negative coordinates, direction-term forks; frame-id
+                       gaps; empty frames and mid-stream frame-0 resets; one object) through the ORACLE tracker with
+                       the twelve option sets of TRACKER_OPTIONS: rows per (stream, option set) and, per step, whether
+                       a confirmed NaN track sat in the association and whether a row scan met the 1e6 NaN sentinel
 Nothing here is produced by product code (stereotracking_amd/ supplies only the seeded synthetic INPUTS).
 Run:  python tests/golden/make_golden.py [name ...]   (deterministic; CI checks the files are reproduced)."""
 import os
@@ -139,23 +144,62 @@ SHIPPED_TRACKER = dict(obj_score_thr=0.3, init_track_thr=0.7, weight_iou_with_de
 def run_oracle_tracker(det, num_frames, **cfg):
     """The ORACLE tracker (oracle/tracker.py, the restatement of the reference classes) over a detection stream.
     -> rows [t, id, x1,y1,x2,y2, score, depth, scale]."""
-    from oracle import tracker as otr
+    return run_oracle_steps(det, np.arange(num_frames), **cfg)[0]
+
+
+def run_oracle_steps(det, frame_ids, probe=False, **cfg):
+    """The ORACLE tracker over a stream of STEPS: step s feeds the rows det[det[:, 0] == s] with frame id frame_ids[s];
+    frame_ids[s] == -1 means the sequence sits this step out (no call).  Column 0 of the rows is the step.
+    -> (rows [s, id, x1,y1,x2,y2, score, depth, scale], nan_live (S,) int8, sentinel (S,) int8).
+    nan_live[s]: the step ran the association (non-empty branch, >= 1 candidate) while a confirmed track's Kalman mean
+    held a NaN, i.e. a row of NaN costs sat in a live cost matrix.  sentinel[s]: a row scan of the augmenting row
+    reduction met a reduced cost >= 1e6 (the NaN -> 1e6 entries), the condition on which csrc/batched_assoc.hip's
+    reduce_rows hands the row to its serial scan (probe=True only: the probe boxes every cost entry, slow on big
+    matrices; both flags stay 0 otherwise)."""
+    from oracle import lapjv as olap, tracker as otr
 
     class _Model:
         motion = otr.KalmanFilter()
 
+    hit = [False]
+
+    class _Probe(float):        # a cost entry of a row that _carr_dense scans: flags `entry - v[j] >= 1e6`
+        def __sub__(self, other):
+            r = float(self) - other
+            if not r < olap.LARGE:
+                hit[0] = True
+            return r
+
+    carr = olap._carr_dense
+
+    def probed(n, cost, *args):
+        return carr(n, [[_Probe(c) for c in row] for row in cost], *args)
+
     trk = otr.OCSORTTracker_Disparity(**cfg)
-    out = []
-    for t in range(num_frames):
-        d = det[det[:, 0] == t]
-        inst = otr.Instances(bboxes=torch.from_numpy(d[:, 1:5].copy()), scores=torch.from_numpy(d[:, 5].copy()),
-                             labels=torch.zeros(len(d), dtype=torch.long), scales=torch.from_numpy(d[:, 7].copy()),
-                             depth=torch.from_numpy(d[:, 6].copy()))
-        r = trk.track(_Model(), None, None, otr.Sample(t, inst))
-        for i in range(len(r.instances_id)):
-            out.append([t, int(r.instances_id[i]), *r.bboxes[i].tolist(), float(r.scores[i]), float(r.depth[i]),
-                        float(r.scales[i])])
-    return np.asarray(out, np.float64).reshape(-1, 9)
+    out, nan_live, sentinel = [], np.zeros(len(frame_ids), np.int8), np.zeros(len(frame_ids), np.int8)
+    if probe:
+        olap._carr_dense = probed
+    try:
+        for s, fid in enumerate(frame_ids):
+            if fid < 0:
+                continue
+            d = det[det[:, 0] == s]
+            cand = (d[:, 5] > cfg.get('obj_score_thr', 0.3)) & ((d[:, 3] - d[:, 1]) * (d[:, 4] - d[:, 2]) > 100)
+            if fid != 0 and trk.tracks and cand.any():
+                nan_live[s] = any(not t.tentative and np.isnan(np.asarray(t.mean, np.float64)).any()
+                                  for t in trk.tracks.values())
+            inst = otr.Instances(bboxes=torch.from_numpy(d[:, 1:5].copy()), scores=torch.from_numpy(d[:, 5].copy()),
+                                 labels=torch.zeros(len(d), dtype=torch.long), scales=torch.from_numpy(d[:, 7].copy()),
+                                 depth=torch.from_numpy(d[:, 6].copy()))
+            hit[0] = False
+            r = trk.track(_Model(), None, None, otr.Sample(int(fid), inst))
+            sentinel[s] = hit[0]
+            for i in range(len(r.instances_id)):
+                out.append([s, int(r.instances_id[i]), *r.bboxes[i].tolist(), float(r.scores[i]), float(r.depth[i]),
+                            float(r.scales[i])])
+    finally:
+        olap._carr_dense = carr
+    return np.asarray(out, np.float64).reshape(-1, 9), nan_live, sentinel
 
 
 def tracker_sequence():
@@ -164,6 +208,152 @@ def tracker_sequence():
     T = 64
     det = detection_stream(51, T)
     return dict(detections=det, tracks=run_oracle_tracker(det, T, **SHIPPED_TRACKER), num_frames=T)
+
+
+TRACKER_OPTIONS = {
+    'shipped': SHIPPED_TRACKER,
+    'reference_defaults': dict(SHIPPED_TRACKER, weight_iou_with_det_scores=True, match_iou_thr=0.3,
+                               num_frames_retain=10),
+    'vel_delta_t_0': dict(SHIPPED_TRACKER, vel_delta_t=0),
+    'vel_delta_t_1': dict(SHIPPED_TRACKER, vel_delta_t=1),
+    'vel_delta_t_7': dict(SHIPPED_TRACKER, vel_delta_t=7),
+    'num_tentatives_1': dict(SHIPPED_TRACKER, num_tentatives=1),
+    'num_tentatives_5': dict(SHIPPED_TRACKER, num_tentatives=5),
+    'num_frames_retain_1': dict(SHIPPED_TRACKER, num_frames_retain=1),
+    'num_frames_retain_2': dict(SHIPPED_TRACKER, num_frames_retain=2),
+    'vel_consist_weight_0': dict(SHIPPED_TRACKER, vel_consist_weight=0.0),
+    'vel_consist_weight_1': dict(SHIPPED_TRACKER, vel_consist_weight=1.0),
+    'match_iou_thr_0.7': dict(SHIPPED_TRACKER, match_iou_thr=0.7),
+}
+"""Tracker option sets of tracker_options.npz: the shipped one, the reference's constructor defaults
+(ocsort_tracker_disparity.py:45-49 with base_tracker.py's num_frames_retain=10), and one option moved at a time."""
+
+
+def nan_detection_row():
+    """(box (4,), depth, scale) of a detection as the product emits it for a box with ONE valid pixel whose corner
+    means exceed it: extract_depth's empty segment gives NaN depth, NaN scale and an all-NaN scaled box."""
+    disp = np.zeros((1, 3, 40, 60), np.float32)
+    disp[:, :, 12, 20] = 20.0                     # the one pixel with 0 < depth < 150; the corners are disparity 0
+    d, s, sb = odepth.bbox_postp_depth(torch.tensor([[15.0, 8.0, 31.0, 22.0]]), torch.from_numpy(disp))
+    box, depth, scale = sb[0].numpy().astype(np.float32), np.float32(d[0]), np.float32(s[0])
+    assert np.isnan(box).all() and np.isnan(depth) and np.isnan(scale), 'extract_depth no longer gives a NaN row'
+    return box, depth, scale
+
+
+def direction_forks(rows, S):
+    """Adds two objects that move right, turn up for two or three frames and right again, and on the frame after
+    that are seen TWICE: the Kalman prediction shifted `delta` up and shifted `delta` right.  The two IoU costs are
+    equal, so the direction term decides which detection keeps the track, and the velocity and the observation it
+    reads are obs[-1 - vel_delta_t]: at both forks vel_delta_t 1 and 7 keep the right-shifted box, 3 (and 0) the
+    up-shifted one.
+    The prediction comes from the ORACLE tracker (shipped options) on the rows before the fork."""
+    from oracle import tracker as otr
+    step = {'R': (6.0, 0.0), 'U': (0.0, -6.0)}
+    for (x0, y0), moves, delta in (((700.0, 300.0), 'R' * 9 + 'UUR', 10.0), ((700.0, 600.0), 'R' * 8 + 'UUUR', 14.0)):
+        fork = len(moves) + 1
+        pos = [np.array([x0, y0])]
+        for m in moves + 'R' * (S - len(moves)):
+            pos.append(pos[-1] + step[m])
+        obj = [[t, *pos[t], *(pos[t] + 30), 0.9, 15.0, 1.0] for t in range(S) if t != fork]
+        rows = np.concatenate([rows, np.asarray(obj, np.float32)])
+        rows = rows[np.argsort(rows[:, 0], kind='stable')]
+        last = np.asarray([*pos[fork - 1], *(pos[fork - 1] + 30)], np.float32)
+        trk = next(t for t in _oracle_tracks(rows[rows[:, 0] < fork], fork)
+                   if np.array_equal(t.bboxes[-1][0].numpy(), last))
+        mean = trk.mean[:4] + trk.mean[4:]                                        # KalmanFilter.predict of the mean
+        pred = otr.bbox_cxcyah_to_xyxy(torch.from_numpy(mean[None]).float())[0].numpy()
+        fork_rows = [[fork, *(pred + np.float32([0, -delta, 0, -delta])), 0.9, 15.0, 1.0],
+                     [fork, *(pred + np.float32([delta, 0, delta, 0])), 0.9, 15.0, 1.0]]
+        rows = np.concatenate([rows, np.asarray(fork_rows, np.float32)])
+        rows = rows[np.argsort(rows[:, 0], kind='stable')]
+    return rows
+
+
+def _oracle_tracks(det, num_frames):
+    """The ORACLE tracker's live tracks after num_frames frames of `det` (shipped options)."""
+    from oracle import tracker as otr
+
+    class _Model:
+        motion = otr.KalmanFilter()
+
+    trk = otr.OCSORTTracker_Disparity(**SHIPPED_TRACKER)
+    for t in range(num_frames):
+        d = det[det[:, 0] == t]
+        inst = otr.Instances(bboxes=torch.from_numpy(d[:, 1:5].copy()), scores=torch.from_numpy(d[:, 5].copy()),
+                             labels=torch.zeros(len(d), dtype=torch.long), scales=torch.from_numpy(d[:, 7].copy()),
+                             depth=torch.from_numpy(d[:, 6].copy()))
+        trk.track(_Model(), None, None, otr.Sample(t, inst))
+    return list(trk.tracks.values())
+
+
+def tracker_option_streams():
+    """The six detection streams of tracker_options.npz: name -> (rows [step, x1,y1,x2,y2, score, depth, scale] float32,
+    frame_ids (S,) int32 with -1 = the sequence has no frame in that step)."""
+    S = 48
+    steps = np.arange(S, dtype=np.int32)
+    out = {}
+    # a) occlusion + exact duplicates (assignment ties)
+    out['occlusion'] = (detection_stream(71, S, K=8, occlusion=(2, 12, 20), duplicates=True), steps.copy())
+    # b) NaN rows: a confirmed NaN track from frame 0, NaN rows above / below init_track_thr later, and empty frames
+    # 20-22 after which the short-retain configs restart from an empty tracker (a tentative NaN track at frame 23)
+    box, dep, scl = nan_detection_row()
+    base = detection_stream(72, S, K=6, occlusion=(1, 10, 16))
+    base = base[(base[:, 0] < 20) | (base[:, 0] > 22)]
+    nan_at = {0: [0.9], 5: [0.9, 0.5], 9: [0.2], 17: [0.75], 23: [0.95], 30: [0.5, 0.9], 41: [0.8]}
+    rows = []
+    for t in range(S):
+        cur = [r for r in base if r[0] == t]
+        for k, sc in enumerate(nan_at.get(t, [])):
+            nan_row = np.array([t, *box, sc, dep, scl], np.float32)
+            cur.insert(0 if k == 0 else len(cur), nan_row)      # first in the frame and last in the frame
+        rows += cur
+    out['nan'] = (np.asarray(rows, np.float32), steps.copy())
+    # c) the area rule's boundary (10 x 10 = 100 exactly vs one ulp taller), a zero-width box, negative coordinates,
+    # and the two direction-term forks
+    rng = np.random.RandomState(73)
+    y2_up = np.nextafter(np.float32(210), np.float32(300))     # 210 + 1 ulp: (y2 - y1) * 10 > 100 in float32
+    rows = []
+    for t in range(S):
+        x = np.float32(300 + t)
+        rows.append([t, 100 + 2.5 * t, 100 + 1.5 * t, 140 + 2.5 * t, 150 + 1.5 * t, 0.9, 20.0, 1.0])  # always there
+        rows.append([t, x, 200, x + 10, 210 if t % 3 == 1 else y2_up, 0.8, 30.0, 1.0])     # area 100 / 100 + ulp
+        rows.append([t, 500 + t, 400, 500 + t, 430, 0.85, 25.0, 1.0])                       # zero width
+        rows.append([t, -80 + 3 * t, -60 + 2 * t, -40 + 3 * t, -10 + 2 * t, 0.8, 12.0, 1.0])  # sum < 0 until t = 19
+        rows.append([t, -25 + rng.normal(0, 0.3), 600, 15 + rng.normal(0, 0.3), 640, 0.75, 40.0, 1.0])  # straddles x = 0
+        if t % 4 == 2:
+            rows.append([t, x, 250, x + 10, 260, 0.8, 30.0, 1.0])                           # area 100 only
+    out['boundary'] = (direction_forks(np.asarray(rows, np.float32), S), steps.copy())
+    # d) frame-id gaps: the sequence sits out steps 10-12, 30 and 38-42, and resumes with the larger frame id
+    det = detection_stream(74, S, K=6, occlusion=(3, 20, 26))
+    fids = steps.copy()
+    fids[[10, 11, 12, 30, 38, 39, 40, 41, 42]] = -1
+    out['gaps'] = (det[fids[det[:, 0].astype(int)] >= 0], fids)
+    # e) empty frames mid-stream (steps 8, 9, 20), a second frame 0 at step 24 and a third, EMPTY, frame 0 at step 40
+    det = detection_stream(75, S, K=5, occlusion=(0, 12, 18), duplicates=True)
+    det = det[~np.isin(det[:, 0], [8, 9, 20, 40])]
+    out['empty_reset'] = (det, np.concatenate([np.arange(24), np.arange(16), np.arange(8)]).astype(np.int32))
+    # f) one object: 1 x 1 assignments (1 x 2 on the duplicate frames), and an occlusion (1 x 0 stages)
+    out['single'] = (detection_stream(76, S, K=1, occlusion=(0, 20, 26), duplicates=True), steps.copy())
+    return out
+
+
+def tracker_options():
+    """Every stream of tracker_option_streams through the ORACLE tracker with every option set of TRACKER_OPTIONS:
+    rows [step, id, box (4), score, depth, scale] per (stream, config), and the per-step NaN / sentinel flags."""
+    import json
+    out = dict(configs=np.asarray(json.dumps(TRACKER_OPTIONS, sort_keys=True)))
+    streams = tracker_option_streams()
+    out['streams'] = np.asarray(sorted(streams))
+    for name, (det, fids) in streams.items():
+        out[f'{name}__detections'], out[f'{name}__frame_ids'] = det, fids
+        for cname, cfg in TRACKER_OPTIONS.items():
+            rows, nan_live, sentinel = run_oracle_steps(det, fids, probe=True, **cfg)
+            out[f'{name}__{cname}__tracks'] = rows
+            out[f'{name}__{cname}__nan_live'] = nan_live
+            out[f'{name}__{cname}__sentinel'] = sentinel
+            print(f'  {name:12s} {cname:22s} {len(rows):4d} rows {len(set(rows[:, 1].tolist())):3d} ids '
+                  f'nan_live {int(nan_live.sum()):2d} sentinel {int(sentinel.sum()):2d}')
+    return out
 
 
 def lapjv_ties():
@@ -351,7 +541,8 @@ def shell_sequence():
 if __name__ == '__main__':
     c_oracle.build()
     for name, fn in (('shell_sequence', shell_sequence), ('config2_sequence', config2_sequence), ('detector_tiny', detector_tiny), ('decode_nms', decode_nms), ('box_depth', box_depth),
-                     ('costvolume', costvolume), ('tracker_sequence', tracker_sequence), ('lapjv_ties', lapjv_ties)):
+                     ('costvolume', costvolume), ('tracker_sequence', tracker_sequence), ('lapjv_ties', lapjv_ties),
+                     ('tracker_options', tracker_options)):
         if len(sys.argv) > 1 and name not in sys.argv[1:]:
             continue
         np.savez_compressed(os.path.join(HERE, name + '.npz'), **fn())
