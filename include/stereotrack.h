@@ -652,6 +652,66 @@ int st_sgbm_speckle(const int16_t* in_dev, int N, int h, int w, int max_size, in
                     int16_t* out_dev, float* disp_postp_dev, int H, int W, int* status_dev, st_stream_t stream);
 
 /* ----------------------------------------------------------------------
+ * 12. COCO bbox evaluation (the configs' evaluator, mmdet.CocoMetric -> pycocotools COCOeval), restated from
+ *     pycocotools / mmdet 3.0.0rc4 [upstream-memory] in csrc/coco_eval.hip; the rules are listed in
+ *     tests/coco_eval_ref.py and DESIGN.md "COCO bbox evaluation".  fp64 and integer counts throughout: the outputs
+ *     are reproducible to the bit.
+ *   rows     detections: float32 xyxy boxes (D, 4), float32 scores, int labels in [0, num_cats), int image index,
+ *            NON-DECREASING (the concatenation of the per-image results in image order; equal scores keep row order);
+ *            ground truth: float64 xywh (G, 4), float64 area, int crowd flag, int category, int image index
+ *            (non-decreasing), on the device, plus host copies of the image index and category (checked before launch).
+ *   tables   iou_thrs (T), area_rng (A, 2) [lo, hi], rec_thrs (R) fp64 on the device; max_dets (M) ints on the HOST,
+ *            non-decreasing: the match is made at max_dets[M - 1], entry m keeps the first max_dets[m] of a group.
+ *            T * A <= 64 (one lane of a wave per pair), A <= 16, M <= 16, R <= 128.
+ *   limits   at most st_coco_max_gt() = ST_COCO_MAX_GT ground-truth boxes per (image, category): ST_ERR_INVALID above.
+ *   outputs  det_rank (D) rank inside the (image, category) group, -1 beyond max_dets[M - 1]; det_matched /
+ *            det_ignored (D) 64-bit tables, bit t * A + a (0 for rank -1); npig (K, A); precision (T, R, K, A, M),
+ *            recall (T, K, A, M), scores (T, R, K, A, M) fp64, -1 where npig == 0.  Every cell is written.
+ *   status   4 ints on the device, 0 = fine.  [0] bits: 1 det_img / 2 gt_img decreasing or out of range, 4 non-finite
+ *            detection ([1] = D - its first row), 8 label out of range ([2] = D - row), 16 ground-truth overflow,
+ *            32 gt category out of range.  Non-zero: the other outputs are not valid.
+ *   Three stages, each enqueued on `stream` with a launch count independent of num_images and no host wait:
+ *   st_coco_prepare (offsets, ranks, npig), st_coco_match (the two tables), st_coco_accumulate (sort + curves).
+ *   ws: caller-owned device workspace of st_coco_workspace_bytes(args), shared by the three calls.
+ * ---------------------------------------------------------------------- */
+#define ST_COCO_MAX_GT 256
+typedef struct StCocoArgs {
+  int struct_size;              /* sizeof(StCocoArgs) */
+  int num_images, num_cats, num_dets, num_gts;
+  int T, A, M, R;
+  const float* det_boxes;
+  const float* det_scores;
+  const int* det_labels;
+  const int* det_img;
+  const double* gt_boxes;
+  const double* gt_area;
+  const int* gt_crowd;
+  const int* gt_cat;
+  const int* gt_img;
+  const int* gt_img_host;
+  const int* gt_cat_host;
+  const double* iou_thrs;
+  const double* area_rng;
+  const double* rec_thrs;
+  const int* max_dets;          /* host */
+  void* ws;
+  size_t ws_bytes;
+  int* det_rank;
+  unsigned long long* det_matched;
+  unsigned long long* det_ignored;
+  int* npig;
+  double* precision;
+  double* recall;
+  double* scores;
+  int* status;
+} StCocoArgs;
+int st_coco_max_gt(void);
+size_t st_coco_workspace_bytes(const StCocoArgs* args);
+int st_coco_prepare(const StCocoArgs* args, st_stream_t stream);
+int st_coco_match(const StCocoArgs* args, st_stream_t stream);
+int st_coco_accumulate(const StCocoArgs* args, st_stream_t stream);
+
+/* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call
  * (mmtrack/datasets/transforms/loading_disparity.py:74-75 uint16 disparity, :213-215 uint16 depth; mmcv's

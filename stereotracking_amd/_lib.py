@@ -65,6 +65,16 @@ class StSgbmParams(C.Structure):
                 ('color', C.c_int)]
 
 
+class StCocoArgs(C.Structure):
+    _fields_ = [('struct_size', C.c_int), ('num_images', C.c_int), ('num_cats', C.c_int), ('num_dets', C.c_int),
+                ('num_gts', C.c_int), ('T', C.c_int), ('A', C.c_int), ('M', C.c_int), ('R', C.c_int)] + \
+        [(n, C.c_void_p) for n in ('det_boxes', 'det_scores', 'det_labels', 'det_img', 'gt_boxes', 'gt_area', 'gt_crowd',
+                                   'gt_cat', 'gt_img', 'gt_img_host', 'gt_cat_host', 'iou_thrs', 'area_rng', 'rec_thrs',
+                                   'max_dets', 'ws')] + [('ws_bytes', C.c_size_t)] + \
+        [(n, C.c_void_p) for n in ('det_rank', 'det_matched', 'det_ignored', 'npig', 'precision', 'recall', 'scores',
+                                   'status')]
+
+
 class StDecodeDesc(C.Structure):
     _fields_ = [
         ('struct_size', C.c_int), ('batch', C.c_int), ('num_levels', C.c_int),
@@ -176,6 +186,11 @@ _PROTOS = {
     'st_box_depth_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'st_pack_records': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'st_box_depth': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp]),
+    'st_coco_max_gt': (_i, []),
+    'st_coco_workspace_bytes': (_sz, [C.POINTER(StCocoArgs)]),
+    'st_coco_prepare': (_i, [C.POINTER(StCocoArgs), _vp]),
+    'st_coco_match': (_i, [C.POINTER(StCocoArgs), _vp]),
+    'st_coco_accumulate': (_i, [C.POINTER(StCocoArgs), _vp]),
     'st_box_depth_method': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _i]),
 }
 

@@ -29,6 +29,7 @@ from .motion import KalmanFilter  # noqa: F401  (registers the motion model)
 from . import detectors  # noqa: F401  (registers detector / backbone / neck / head)
 from . import stereo as _stereo  # noqa: F401  (registers StereoCostVolume)
 from . import sgbm as _sgbm  # noqa: F401  (registers StereoSGBM)
+from . import coco_metric as _coco_metric  # noqa: F401  (registers CocoMetric in METRICS)
 
 
 def stack_batch(tensors, pad_size_divisor=0, pad_value=0):
