@@ -712,6 +712,55 @@ int st_coco_match(const StCocoArgs* args, st_stream_t stream);
 int st_coco_accumulate(const StCocoArgs* args, st_stream_t stream);
 
 /* ----------------------------------------------------------------------
+ * 13. Multi-stream tracking (MultiStreamTracker): the device path of one TICK - at most one frame from each of
+ *     `streams` videos - between the dense launch plan, the batched association of section 9 and the tick's ONE
+ *     device->host copy (csrc/stream_track.hip).  The tick's frames occupy SLOTS: slot i is frame i % chunk of dense
+ *     chunk i / chunk; the routing (stream_of_slot, frame_ids) and the chunks' buffer pointers are HOST arrays that
+ *     travel in the kernel arguments - a tick needs no host->device copy.  Three launches, each enqueued on `stream`
+ *     without a host wait:
+ *   st_stream_gather   chunk_records[c] = the chunk's frame records (st_pack_records mode 2, (chunk, det_rows + 1, 13))
+ *                      -> the tracker's input BY STREAM: dets (streams, max_dets, 8), counts (streams) = the TRUE
+ *                      number kept, unclipped (above max_dets st_batched_tracker_step reports status 2), -1 for a stream
+ *                      without a frame; frame_ids (streams); and the detection rows of the tick record.
+ *   st_stream_unscale  the tracker's out_rows / out_counts -> scale_bbox(box, 1 / scale) (reference
+ *                      mmtrack/models/mot/ocsort_disparity.py:95-97; the same single fp32 operations as
+ *                      st_tracker_track_records) BY SLOT: boxes (chunk * num_chunks, max_dets, 4), box_counts
+ *                      (chunk * num_chunks; 0 for padding slots) - st_box_depth's input, chunk c at slot c * chunk.
+ *   st_stream_record   chunk_depth[c] / chunk_gt_depth[c] (NULL array: gt_depth = depth) = st_box_depth's depth output
+ *                      of chunk c, (chunk, max_dets) -> the tick record.
+ *   Tick record (st_stream_record_bytes, one buffer):
+ *     int64   ids    [streams][max_dets]                     instances_id
+ *     int32   header [streams][ST_STREAM_HDR_INTS]           track rows (-1: no frame in this tick), detections kept
+ *                                                            (true count), tracker status (section 9), frame id
+ *     float32 tracks [streams][max_dets][ST_STREAM_ROW_FLOATS]   unscaled box (4), score, label, scale, depth,
+ *                                                            gt depth, 0
+ *     float32 dets   [streams][det_rows][ST_STREAM_DET_FLOATS]   unscaled box (4), score, label, kept prior index, 0
+ *   Rows past a stream's counts are not written.
+ * ---------------------------------------------------------------------- */
+#define ST_STREAM_MAX_STREAMS 128
+#define ST_STREAM_HDR_INTS 4
+#define ST_STREAM_ROW_FLOATS 10
+#define ST_STREAM_DET_FLOATS 8
+typedef struct StStreamTick {
+  int struct_size;                 /* sizeof(StStreamTick) */
+  int streams;                     /* <= ST_STREAM_MAX_STREAMS */
+  int chunk, num_chunks;           /* chunk * num_chunks slots, <= ST_STREAM_MAX_STREAMS */
+  int max_dets;                    /* rows per stream of the tracker's input and output */
+  int det_rows;                    /* detection rows of a frame record (the dense plan's max_det) */
+  const int32_t* stream_of_slot;   /* host, [chunk * num_chunks]: stream in [0, streams), each at most once; -1 = padding */
+  const int32_t* frame_ids;        /* host, [streams]: read for the streams that have a slot */
+} StStreamTick;
+size_t st_stream_record_bytes(int streams, int max_dets, int det_rows);
+int st_stream_gather(const StStreamTick* tick, const float* const* chunk_records, float* dets_dev, int32_t* counts_dev,
+                     int32_t* frame_ids_dev, void* record_dev, st_stream_t stream);
+int st_stream_unscale(const StStreamTick* tick, const float* rows_dev, const int32_t* out_counts_dev, float* boxes_dev,
+                      int32_t* box_counts_dev, st_stream_t stream);
+int st_stream_record(const StStreamTick* tick, const float* rows_dev, const int64_t* ids_dev,
+                     const int32_t* out_counts_dev, const int32_t* status_dev, const int32_t* counts_dev,
+                     const float* boxes_dev, const float* const* chunk_depth, const float* const* chunk_gt_depth,
+                     void* record_dev, st_stream_t stream);
+
+/* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call
  * (mmtrack/datasets/transforms/loading_disparity.py:74-75 uint16 disparity, :213-215 uint16 depth; mmcv's

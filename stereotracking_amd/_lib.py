@@ -75,6 +75,11 @@ class StCocoArgs(C.Structure):
                                    'status')]
 
 
+class StStreamTick(C.Structure):
+    _fields_ = [('struct_size', C.c_int), ('streams', C.c_int), ('chunk', C.c_int), ('num_chunks', C.c_int),
+                ('max_dets', C.c_int), ('det_rows', C.c_int), ('stream_of_slot', C.c_void_p), ('frame_ids', C.c_void_p)]
+
+
 class StDecodeDesc(C.Structure):
     _fields_ = [
         ('struct_size', C.c_int), ('batch', C.c_int), ('num_levels', C.c_int),
@@ -192,6 +197,10 @@ _PROTOS = {
     'st_coco_match': (_i, [C.POINTER(StCocoArgs), _vp]),
     'st_coco_accumulate': (_i, [C.POINTER(StCocoArgs), _vp]),
     'st_box_depth_method': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _i]),
+    'st_stream_record_bytes': (_sz, [_i, _i, _i]),
+    'st_stream_gather': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp, _vp]),
+    'st_stream_unscale': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp]),
+    'st_stream_record': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

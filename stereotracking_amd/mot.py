@@ -822,3 +822,6 @@ class OCSORT_Disparity(nn.Module):
         if self.results_csv is not None:
             append_prediction_results(self.results_csv, outs)
         return outs
+
+
+from . import multistream as _multistream  # noqa: E402,F401  (registers MultiStreamTracker; it wraps the shell above)
