@@ -97,6 +97,12 @@ int st_conv2d_nhwc_variant(const StConvDesc* d, st_stream_t stream, int variant)
  * U = G g G^T is evaluated in fp64 on the folded fp32 weights and rounded once. */
 size_t st_wino_packed_floats(int Cout, int Cin);
 int st_wino_pack_weights(const float* packed_wgt_host, int Cout, int Cin, float* out_host);
+/* GROUPED Winograd launch: n = 2..6 INDEPENDENT layers (their own shapes, tensors and weights) as ONE grid - what the
+ * detector plan does with one tower depth of the head over the three levels (instances 48 / 49).  Every layer must be
+ * a wide Winograd layer without a K tail: 3x3 / stride 1 / pad 1, wgt_wino_dev set, Cout % 64 == 0, Cin % 32 == 0, no
+ * residual / split / upsample store.  Each output is bit-identical to st_conv2d_nhwc_variant(&descs[k], stream, 43).
+ * ST_ERR_INVALID (nothing launched) when a layer or n does not qualify. */
+int st_conv3x3_wino_group(const StConvDesc* descs, int n, st_stream_t stream);
 
 /* Fused pair of 1x1 convolutions for the narrow high-resolution CSP layers: `b` (Cin = 32, Cout <= 32) consumes
  * output channels [0, 32) of `a` (Cin 32 or 64, 32 < Cout <= 64, no residual) - the CSPLayer main_conv ->
@@ -295,6 +301,12 @@ int st_detector_num_ops(const StDetector* det);
 int st_detector_op_times(StDetector* det, int cap, float* ms, int* kind, int* variant, double* macs,
                          int* phase);
 int st_detector_op_desc(const StDetector* det, int i, char* buf, int cap);
+/* Which launch computed each op at the most recent forward (no timing events needed): owner[i] = i for an op with a
+ * launch of its own, the index of the FIRST op for the riders of a fused (45, 56), chained (41, 46) or grouped
+ * (48 / 49) launch, -1 for an op that has not run yet.  variant (may be NULL) = the instance per op as
+ * st_detector_op_times reports it.  A chained rider reports the same instance as its owner; only `owner` tells a chain
+ * from two launches. */
+int st_detector_op_owner(const StDetector* det, int cap, int* owner, int* variant);
 /* Measure every valid conv tile variant on every conv op's real shape and keep the fastest
  * (host-synchronous; call once after st_detector_finalize, never inside a timed region). */
 /* Split-operand instances (tile variants 50-55 of st_conv2d_nhwc_variant): the same implicit GEMM with every fp32 operand
@@ -314,10 +326,30 @@ const char* st_conv_variant_signature(int id); /* template args of the variant's
 int st_detector_get_tuning(const StDetector* det, int* variants, int cap);
 int st_detector_set_tuning(StDetector* det, const int* variants, int n);
 /* Internal NHWC activations inside the workspace (valid after forward); name in
- * {"stage1_rgb","stage1_fused","stage2","stage3","stage4","p3","p4","p5"}.  Pixel p, channel c
+ * {"stage1_rgb","stage1_fused","stage2","stage3","stage4","p3_inner","p3","p4","p5"}.  Pixel p, channel c
  * is ptr[p*ld + c]. */
 int st_detector_tap(const StDetector* det, const char* name, const void* workspace_dev,
                     const float** ptr_dev, int* N, int* C, int* H, int* W, int* ld);
+/* The prediction convolutions of the decoupled head on their own (instance 47 of the plan): per level conv_cls
+ * (feat -> 1) on the cls tower and conv_reg | conv_obj (feat -> 4 | 1) on the reg tower, all three levels in ONE
+ * launch.  Pixel m of a level reads cls_dev[m * cls_ld + cls_off + c] / reg_dev[...], c < feat, and writes its 32-byte
+ * head row out_dev[m * 8 + 0..5] = [cls | x y w h | obj]; floats 6, 7 of a row and rows >= M are not written.
+ * wgt_* / bias_* = st_conv_pack_weights of the 1 x feat and the stacked 5 x feat (reg rows, then obj) 1x1 weights.
+ * feat in {96, 128, 256} and num_classes == 1 only (ST_ERR_INVALID otherwise, nothing launched); tensors 16-byte
+ * aligned, strides / offsets multiples of 4, M > 0. */
+typedef struct StHeadPredLevel {
+  const float* cls_dev;
+  int cls_ld, cls_off;
+  const float* reg_dev;
+  int reg_ld, reg_off;
+  const float* wgt_cls_dev;
+  const float* bias_cls_dev;
+  const float* wgt_reg_dev;
+  const float* bias_reg_dev;
+  float* out_dev;
+  int M;
+} StHeadPredLevel;
+int st_head_pred(const StHeadPredLevel levels[3], int feat, int num_classes, st_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 4. Decode + score filter + sort + NMS.

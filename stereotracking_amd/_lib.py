@@ -80,6 +80,14 @@ class StStreamTick(C.Structure):
                 ('max_dets', C.c_int), ('det_rows', C.c_int), ('stream_of_slot', C.c_void_p), ('frame_ids', C.c_void_p)]
 
 
+class StHeadPredLevel(C.Structure):
+    _fields_ = [('cls_dev', C.c_void_p), ('cls_ld', C.c_int), ('cls_off', C.c_int),
+                ('reg_dev', C.c_void_p), ('reg_ld', C.c_int), ('reg_off', C.c_int),
+                ('wgt_cls_dev', C.c_void_p), ('bias_cls_dev', C.c_void_p),
+                ('wgt_reg_dev', C.c_void_p), ('bias_reg_dev', C.c_void_p),
+                ('out_dev', C.c_void_p), ('M', C.c_int)]
+
+
 class StDecodeDesc(C.Structure):
     _fields_ = [
         ('struct_size', C.c_int), ('batch', C.c_int), ('num_levels', C.c_int),
@@ -108,6 +116,9 @@ _PROTOS = {
     'st_last_error': (C.c_char_p, []),
     'st_conv2d_nhwc': (_i, [C.POINTER(StConvDesc), _vp]),
     'st_conv2d_nhwc_variant': (_i, [C.POINTER(StConvDesc), _vp, _i]),
+    'st_conv3x3_wino_group': (_i, [C.POINTER(StConvDesc), _i, _vp]),
+    'st_head_pred': (_i, [C.POINTER(StHeadPredLevel), _i, _i, _vp]),
+    'st_detector_op_owner': (_i, [_vp, _i, _vp, _vp]),
     'st_conv1x1_chain': (_i, [C.POINTER(StConvDesc), C.POINTER(StConvDesc), _vp]),
     'st_front_frag_floats': (_sz, [_i, _i]),
     'st_front_pack_frags': (_i, [_vp, _i, _i, _vp]),

@@ -154,6 +154,7 @@ struct Op {
   double macs = 0.0;   // conv MACs of this op
   int variant = -1;    // conv tile variant picked at the last launch
   int tuned = -1;      // measured best variant (st_detector_autotune), -1 = heuristic
+  int owner = -1;      // index of the op whose launch computed this op at the last forward (itself unless it rode along)
   int group = 0;       // sub-batch group (0 = whole batch in one launch)
   bool chain_next = false;  // the NEXT op is a 1x1 conv on this op's out1 (CSP main_conv -> bottleneck conv1):
                             // when both run on the streaming kernel (variant 41), or both on the LDS-resident
@@ -836,6 +837,7 @@ int run_ops(StDetector* det, int phase_lo, int phase_hi, const float* const inpu
           if (det->timing && k > oi) ST_CHECK_HIP(hipEventRecord(det->events[ev_per_op * k], stream));
           if (det->timing) ST_CHECK_HIP(hipEventRecord(det->events[ev_per_op * k + 1], stream));
           det->ops[k].variant = k == oi ? 48 : 49;
+          det->ops[k].owner = (int)oi;
         }
         oi = we;
         continue;
@@ -847,7 +849,7 @@ int run_ops(StDetector* det, int phase_lo, int phase_hi, const float* const inpu
       ++oe;   // a chainable pair outside the sub-batch groups is still launched as one
     const StDetector::Group g = det->groups[first.group];
     for (int sbi = 0; sbi < g.count; ++sbi) {
-      int fused_left = 0, fused_variant = 0;   // ops already computed by a preceding fused launch
+      int fused_left = 0, fused_variant = 0, fused_owner = -1;   // ops already computed by a preceding fused launch
       for (size_t k = oi; k < oe; ++k) {
         Op& o = det->ops[k];
         if (det->timing) ST_CHECK_HIP(hipEventRecord(det->events[ev_per_op * k + 2 * sbi], stream));
@@ -860,6 +862,7 @@ int run_ops(StDetector* det, int phase_lo, int phase_hi, const float* const inpu
         if (!skipped && fused_left > 0) {   // this op was computed by a previous (chained / fused) launch
           --fused_left;
           o.variant = fused_variant;
+          o.owner = fused_owner;
           chained = true;
         } else if (!skipped && o.type == Op::CONV && o.front_next2 && k + 2 < oe && det->force_variant < 0 &&
                    det->allow_front && det->convs[det->ops[k + 1].pc].frag && det->convs[det->ops[k + 2].pc].frag) {
@@ -870,6 +873,7 @@ int run_ops(StDetector* det, int phase_lo, int phase_hi, const float* const inpu
             ST_CHECK(front_fused_launch(da, dm, dc, det->wgt_dev + det->convs[det->ops[k + 1].pc].frag_off,
                                         det->wgt_dev + det->convs[det->ops[k + 2].pc].frag_off, stream));
             o.variant = fused_variant = 45;
+            o.owner = fused_owner = (int)k;
             fused_left = 2;
             chained = true;
           }
@@ -881,6 +885,7 @@ int run_ops(StDetector* det, int phase_lo, int phase_hi, const float* const inpu
           if (csp_tail_applicable(d2, df)) {
             ST_CHECK(csp_tail_launch(d2, df, det->wgt_dev + det->convs[det->ops[k + 1].pc].tail_off, stream));
             o.variant = fused_variant = 56;
+            o.owner = fused_owner = (int)k;
             fused_left = 1;
             chained = true;
           }
@@ -892,11 +897,15 @@ int run_ops(StDetector* det, int phase_lo, int phase_hi, const float* const inpu
           if (o.tuned == 41 ? pw_chain_applicable(da, db) : pwr_chain_applicable(da, db)) {
             ST_CHECK(o.tuned == 41 ? pw_conv_launch(da, stream, &db) : pwr_conv_launch(da, stream, &db));
             o.variant = fused_variant = o.tuned;
+            o.owner = fused_owner = (int)k;
             fused_left = 1;
             chained = true;
           }
         }
-        if (!skipped && !chained) ST_CHECK(launch_op(det, o, sbi * g.sb, inputs, ws, head, stream));
+        if (!skipped && !chained) {
+          ST_CHECK(launch_op(det, o, sbi * g.sb, inputs, ws, head, stream));
+          o.owner = (int)k;
+        }
         if (det->timing) ST_CHECK_HIP(hipEventRecord(det->events[ev_per_op * k + 2 * sbi + 1], stream));
       }
     }
@@ -1034,6 +1043,19 @@ extern "C" int st_detector_op_times(StDetector* det, int cap, float* ms, int* ki
     if (variant) variant[i] = det->ops[i].variant;
     if (macs) macs[i] = det->ops[i].macs;
     if (phase) phase[i] = det->ops[i].phase;
+  }
+  return ST_OK;
+}
+
+// Which launch computed each op at the most recent forward: owner[i] = i for an op with a launch of its own, the index
+// of the first op for the riders of a fused (45, 56), chained (41, 46) or grouped (48 / 49) launch, -1 for an op that
+// has not run yet; variant[i] (may be NULL) = the instance as st_detector_op_times reports it.  Needs no timing events.
+extern "C" int st_detector_op_owner(const StDetector* det, int cap, int* owner, int* variant) {
+  if (!det || !owner) return set_error(ST_ERR_INVALID, "st_detector_op_owner: null argument");
+  ST_REQUIRE(cap >= (int)det->ops.size(), "st_detector_op_owner: capacity %d < %zu ops", cap, det->ops.size());
+  for (size_t i = 0; i < det->ops.size(); ++i) {
+    owner[i] = det->ops[i].owner;
+    if (variant) variant[i] = det->ops[i].variant;
   }
   return ST_OK;
 }

@@ -130,3 +130,22 @@ int head_pred_launch(HeadPredArgs a, int feat, hipStream_t stream) {
 }
 
 }  // namespace st
+
+// The fused prediction launch on its own (tile variant 47 of the detector plan).
+extern "C" int st_head_pred(const StHeadPredLevel* levels, int feat, int num_classes, st_stream_t stream) {
+  if (!levels) return st::set_error(ST_ERR_INVALID, "st_head_pred: null levels");
+  st::HeadPredArgs a{};
+  for (int l = 0; l < 3; ++l) {
+    const StHeadPredLevel& s = levels[l];
+    st::HeadPredLevel& L = a.lv[l];
+    L.cls = s.cls_dev; L.cls_ld = s.cls_ld; L.cls_off = s.cls_off;
+    L.reg = s.reg_dev; L.reg_ld = s.reg_ld; L.reg_off = s.reg_off;
+    L.wc = s.wgt_cls_dev; L.bc = s.bias_cls_dev; L.wr = s.wgt_reg_dev; L.br = s.bias_reg_dev;
+    L.out = s.out_dev; L.M = s.M;
+    ST_REQUIRE(s.cls_off >= 0 && s.reg_off >= 0 && s.cls_off + feat <= s.cls_ld && s.reg_off + feat <= s.reg_ld,
+               "st_head_pred: level %d: channel slice exceeds its row", l);
+  }
+  a.Kpad = st::round_up(feat, 32);
+  a.nc = num_classes;
+  return st::head_pred_launch(a, feat, static_cast<hipStream_t>(stream));
+}

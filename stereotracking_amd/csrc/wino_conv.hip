@@ -785,6 +785,12 @@ int wino_group_launch(const StConvDesc* d, int n, hipStream_t stream) {
 
 }  // namespace st
 
+// The grouped launch on its own (the detector plan runs the head towers through it, tile variants 48 / 49).
+extern "C" int st_conv3x3_wino_group(const StConvDesc* descs, int n, st_stream_t stream) {
+  if (!descs) return st::set_error(ST_ERR_INVALID, "st_conv3x3_wino_group: null descriptors");
+  return st::wino_group_launch(descs, n, static_cast<hipStream_t>(stream));
+}
+
 extern "C" size_t st_wino_packed_floats(int Cout, int Cin) { return st::wino_packed_floats(Cout, Cin); }
 
 extern "C" int st_wino_pack_weights(const float* packed_wgt_host, int Cout, int Cin, float* out_host) {

@@ -156,6 +156,24 @@ class HipDetector:
         arr = (C.c_int * len(variants))(*[int(v) for v in variants])
         check(self.lib.st_detector_set_tuning(self.handle, arr, len(variants)), 'st_detector_set_tuning')
 
+    def launch_report(self):
+        """[(variant, owner)] per op of the most recent forward (st_detector_op_owner; no timing events): the kernel
+        instance that computed the op and the index of the op whose launch did it - the op itself, or the first op of
+        a fused / chained / grouped launch for its riders."""
+        n = self.lib.st_detector_num_ops(self.handle)
+        owner, variant = (C.c_int * n)(), (C.c_int * n)()
+        check(self.lib.st_detector_op_owner(self.handle, n, owner, variant), 'st_detector_op_owner')
+        return list(zip(variant, owner))
+
+    def op_descs(self):
+        """The plan's ops as text (st_detector_op_desc), in launch order."""
+        buf = C.create_string_buffer(512)
+        out = []
+        for i in range(self.lib.st_detector_num_ops(self.handle)):
+            check(self.lib.st_detector_op_desc(self.handle, i, buf, 512), 'st_detector_op_desc')
+            out.append(buf.value.decode())
+        return out
+
     # ---- forward -----------------------------------------------------------------------------
     def _workspace(self, device):
         if self._ws is None or self._ws.device != device:
