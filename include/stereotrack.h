@@ -619,6 +619,19 @@ int st_cmc_flow(const void* prev_planes_dev, const void* curr_planes_dev, int N,
 int st_cmc_estimate(const void* prev_planes_dev, const void* curr_planes_dev, int N, int img_h, int img_w,
                     const StCmcParams* params, void* ws, size_t ws_bytes, float* warps_out_dev, float* mesh_out_dev,
                     unsigned char* inliers_out_dev, st_stream_t stream);
+/* The two later stages of st_cmc_estimate entered directly (the same launches; test-facing, no product caller).
+ * st_cmc_mesh_fit: a device flow field (N, 255, 255, 2) fp32 in place of the two planes, copied into the workspace where
+ * st_cmc_flow leaves its own, then mesh -> fit with `params` (winsize unused); outputs as st_cmc_estimate.  The flow must
+ * be free of NaN: a NaN has no rank, the cell's median is left unset and its mesh row is undefined (as it is for a NaN
+ * out of the Farneback solve, which the regularised determinant rules out for finite planes).
+ * st_cmc_fit: device points (N, P, 4) fp32 {src x, src y, dst x, dst y}, 2 <= P <= 1024, straight into the consensus fit
+ * with its two options; warps and inliers (optional, N x P uint8) as st_cmc_estimate.  Both refuse, before any launch, a
+ * null pointer, N <= 0, a workspace under st_cmc_workspace_bytes(N), and a step / P outside their range. */
+int st_cmc_mesh_fit(const float* flow_dev, int N, int img_h, int img_w, const StCmcParams* params, void* ws,
+                    size_t ws_bytes, float* warps_out_dev, float* mesh_out_dev, unsigned char* inliers_out_dev,
+                    st_stream_t stream);
+int st_cmc_fit(const float* points_dev, int N, int P, float ransac_thr, float min_inlier_ratio, void* ws,
+               size_t ws_bytes, float* warps_out_dev, unsigned char* inliers_out_dev, st_stream_t stream);
 /* The tracker step of section 8 with camera-motion compensation: `warp` (2 x 3, row-major, float64) is applied to every
  * confirmed track's Kalman state right after the predict (reference gmc.py:20-45: mean[0:2] = R mean[0:2] + t,
  * mean[4:6] = R mean[4:6], mean[3], mean[7] *= s = sqrt(max(det R, 1e-12)), cov = M cov M^T); NULL = no warp.  The

@@ -177,6 +177,8 @@ _PROTOS = {
     'st_cmc_front_f32': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'st_cmc_flow': (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     'st_cmc_estimate': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(StCmcParams), _vp, _sz, _vp, _vp, _vp, _vp]),
+    'st_cmc_mesh_fit': (_i, [_vp, _i, _i, _i, C.POINTER(StCmcParams), _vp, _sz, _vp, _vp, _vp, _vp]),
+    'st_cmc_fit': (_i, [_vp, _i, _i, C.c_float, C.c_float, _vp, _sz, _vp, _vp, _vp]),
     'st_sgbm_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'st_sgbm_u8': (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(StSgbmParams), _vp, _sz, _vp, _i, _i, _vp, _vp]),
     'st_sgbm_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(StSgbmParams), _vp, _sz, _vp, _vp, _vp]),

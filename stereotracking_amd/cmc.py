@@ -108,6 +108,38 @@ def estimate(prev, curr, img_h, img_w, params=None, with_mesh=False, ws=None):
     return (warps, mesh, inl) if with_mesh else warps
 
 
+def mesh_fit(flow, img_h, img_w, params=None, with_mesh=False, ws=None):
+    """The estimate entered after the flow (st_cmc_mesh_fit): flow (N, 255, 255, 2) fp32 device tensor -> what
+    estimate() returns for planes with that flow.  Test-facing; the flow must be free of NaN."""
+    p = glme_params(params)
+    if flow.dim() != 4 or tuple(flow.shape[1:]) != (SIDE, SIDE, 2) or flow.dtype != torch.float32 or not flow.is_cuda:
+        raise ValueError('CMC mesh_fit: flow must be a (N, 255, 255, 2) fp32 CUDA tensor')
+    N, dev = int(flow.shape[0]), flow.device
+    ws = _workspace(N, dev) if ws is None else ws
+    warps = torch.empty(N, WARP_FLOATS, device=dev)
+    P = (SIDE // int(p['step'])) ** 2
+    mesh = torch.empty(N, P, 4, device=dev) if with_mesh else None
+    inl = torch.empty(N, P, dtype=torch.uint8, device=dev) if with_mesh else None
+    prm = _params(p)
+    check(_lib.load().st_cmc_mesh_fit(ptr(flow.contiguous()), N, int(img_h), int(img_w), C.byref(prm), ptr(ws),
+                                      ws.numel(), ptr(warps), ptr(mesh), ptr(inl), current_stream()), 'st_cmc_mesh_fit')
+    return (warps, mesh, inl) if with_mesh else warps
+
+
+def fit(points, ransac_thr=DEFAULTS['ransac_thr'], min_inlier_ratio=DEFAULTS['min_inlier_ratio'], ws=None):
+    """The consensus fit alone (st_cmc_fit): points (N, P, 4) fp32 device tensor {src x, src y, dst x, dst y},
+    2 <= P <= 1024 -> warps (N, 8) as estimate(), inliers (N, P) uint8.  Test-facing."""
+    if points.dim() != 3 or points.shape[2] != 4 or points.dtype != torch.float32 or not points.is_cuda:
+        raise ValueError('CMC fit: points must be a (N, P, 4) fp32 CUDA tensor')
+    N, P, dev = int(points.shape[0]), int(points.shape[1]), points.device
+    ws = _workspace(N, dev) if ws is None else ws
+    warps = torch.empty(N, WARP_FLOATS, device=dev)
+    inl = torch.empty(N, P, dtype=torch.uint8, device=dev)
+    check(_lib.load().st_cmc_fit(ptr(points.contiguous()), N, P, float(ransac_thr), float(min_inlier_ratio), ptr(ws),
+                                 ws.numel(), ptr(warps), ptr(inl), current_stream()), 'st_cmc_fit')
+    return warps, inl
+
+
 def warp_or_none(row):
     """One (8,) host row of estimate() -> 2 x 3 float32 warp, or None (fit failed / inlier ratio too low)."""
     row = np.asarray(row, np.float32)

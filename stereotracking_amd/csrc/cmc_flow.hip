@@ -672,13 +672,12 @@ extern "C" int st_cmc_front_u8(const void* const* frames_u8_dev_ptrs_host, int N
   using namespace st;
   ST_REQUIRE(frames_u8_dev_ptrs_host && planes_dev && N > 0 && h > 0 && w > 0 && h <= fh && w <= fw,
              "st_cmc_front_u8: bad argument");
+  for (int i = 0; i < N; ++i)     // every frame before the first launch: a refused call has launched nothing
+    ST_REQUIRE(frames_u8_dev_ptrs_host[i], "st_cmc_front_u8: frame %d is null", i);
   for (int base = 0; base < N; base += kMaxFrames) {
     const int k = N - base < kMaxFrames ? N - base : kMaxFrames;
     FramePtrs fp{};
-    for (int i = 0; i < k; ++i) {
-      fp.p[i] = static_cast<const unsigned char*>(frames_u8_dev_ptrs_host[base + i]);
-      ST_REQUIRE(fp.p[i], "st_cmc_front_u8: frame %d is null", base + i);
-    }
+    for (int i = 0; i < k; ++i) fp.p[i] = static_cast<const unsigned char*>(frames_u8_dev_ptrs_host[base + i]);
     hipLaunchKernelGGL(cmc_front_u8_kernel, dim3(k), dim3(1024), 0, static_cast<hipStream_t>(stream), fp, fh, fw, h, w,
                        static_cast<unsigned char*>(planes_dev) + (size_t)base * kPlane);
   }
@@ -716,29 +715,83 @@ extern "C" int st_cmc_flow(const void* prev_planes_dev, const void* curr_planes_
   return ST_OK;
 }
 
+// ---- the later stages, shared by st_cmc_estimate and the two injection points -------------------------------------
+namespace {
+
+// grid (ceil(2 * 255^2 / 256), N): a caller's flow field into the level-0 flow of every pair's workspace (the inverse of
+// cmc_copy_flow_kernel), so that the mesh reads it where the Farneback launches leave theirs
+__global__ void cmc_load_flow_kernel(FlowGeom g, const float* flow_in, float* ws) {
+  const int n = blockIdx.y;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < 2LL * kPlane) pair_ws(ws, g, n).F[2 * g.lv[0].off + i] = flow_in[(long long)n * 2 * kPlane + i];
+}
+
+int require_estimate_args(const char* who, const StCmcParams* prm, int N, int img_h, int img_w, const void* ws,
+                          size_t ws_bytes, const float* warps_out_dev) {
+  using namespace st;
+  ST_REQUIRE(prm && prm->struct_size == (int)sizeof(StCmcParams), "%s: params struct_size mismatch", who);
+  ST_REQUIRE(warps_out_dev && ws && N > 0 && img_h > 0 && img_w > 0, "%s: bad argument", who);
+  ST_REQUIRE(prm->step >= 8 && prm->step * prm->step <= 256, "%s: step %d must be in 8..16", who, prm->step);
+  ST_REQUIRE(ws_bytes >= st_cmc_workspace_bytes(N), "%s: workspace %zu < %zu bytes", who, ws_bytes,
+             st_cmc_workspace_bytes(N));
+  return ST_OK;
+}
+
+// points (N, P, 4) -> warps (N, ST_CMC_WARP_FLOATS), inliers (N, P; optional); the fit keys live in the workspace
+int launch_fit(const float* points, int N, int P, float ransac_thr, float min_inlier_ratio, void* ws, float* warps,
+               unsigned char* inliers, hipStream_t s) {
+  unsigned long long* keys =
+      reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(ws) + keys_offset(N));
+  const float thr2 = ransac_thr * ransac_thr;
+  ST_CHECK_HIP(hipMemsetAsync(keys, 0, (size_t)N * sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(cmc_fit_score_kernel, dim3(kFitParts, N), dim3(256), 0, s, points, P, thr2, keys);
+  hipLaunchKernelGGL(cmc_fit_kernel, dim3(N), dim3(256), 0, s, points, P, thr2, min_inlier_ratio, keys, warps, inliers);
+  ST_CHECK_HIP(hipGetLastError());
+  return ST_OK;
+}
+
+// the level-0 flow of every pair's workspace -> mesh (into mesh_out, else into the workspace) -> fit
+int launch_mesh_fit(int N, int img_h, int img_w, const StCmcParams* prm, void* ws, float* warps, float* mesh_out,
+                    unsigned char* inliers, hipStream_t s) {
+  const FlowGeom& g = geom();
+  const int gw = kSide / prm->step, P = gw * gw;
+  float* mesh = mesh_out ? mesh_out : static_cast<float*>(ws) + (long long)N * pair_floats(g.S);
+  hipLaunchKernelGGL(cmc_mesh_kernel, dim3(P, N), dim3(64), 0, s, g, prm->step, gw, (double)img_w / kSide,
+                     (double)img_h / kSide, static_cast<float*>(ws), mesh);
+  return launch_fit(mesh, N, P, prm->ransac_thr, prm->min_inlier_ratio, ws, warps, inliers, s);
+}
+
+}  // namespace
+
 extern "C" int st_cmc_estimate(const void* prev_planes_dev, const void* curr_planes_dev, int N, int img_h, int img_w,
                                const StCmcParams* prm, void* ws, size_t ws_bytes, float* warps_out_dev,
                                float* mesh_out_dev, unsigned char* inliers_out_dev, st_stream_t stream) {
-  using namespace st;
-  ST_REQUIRE(prm && prm->struct_size == (int)sizeof(StCmcParams), "st_cmc_estimate: params struct_size mismatch");
-  ST_REQUIRE(warps_out_dev && img_h > 0 && img_w > 0, "st_cmc_estimate: bad argument");
-  ST_REQUIRE(prm->step >= 8 && prm->step <= 16 * 16 && prm->step * prm->step <= 256 && prm->step <= kSide,
-             "st_cmc_estimate: step %d must be in 8..16", prm->step);
+  ST_CHECK(require_estimate_args("st_cmc_estimate", prm, N, img_h, img_w, ws, ws_bytes, warps_out_dev));
   ST_CHECK(st_cmc_flow(prev_planes_dev, curr_planes_dev, N, prm->winsize, ws, ws_bytes, nullptr, nullptr, stream));
+  return launch_mesh_fit(N, img_h, img_w, prm, ws, warps_out_dev, mesh_out_dev, inliers_out_dev,
+                         static_cast<hipStream_t>(stream));
+}
+
+extern "C" int st_cmc_mesh_fit(const float* flow_dev, int N, int img_h, int img_w, const StCmcParams* prm, void* ws,
+                               size_t ws_bytes, float* warps_out_dev, float* mesh_out_dev,
+                               unsigned char* inliers_out_dev, st_stream_t stream) {
+  using namespace st;
+  ST_CHECK(require_estimate_args("st_cmc_mesh_fit", prm, N, img_h, img_w, ws, ws_bytes, warps_out_dev));
+  ST_REQUIRE(flow_dev, "st_cmc_mesh_fit: flow is null");
   const FlowGeom& g = geom();
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  const int gw = kSide / prm->step, P = gw * gw;
-  float* mesh = mesh_out_dev ? mesh_out_dev
-                             : static_cast<float*>(ws) + (long long)N * pair_floats(g.S);
-  hipLaunchKernelGGL(cmc_mesh_kernel, dim3(P, N), dim3(64), 0, s, g, prm->step, gw, (double)img_w / kSide,
-                     (double)img_h / kSide, static_cast<float*>(ws), mesh);
-  unsigned long long* keys =
-      reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(ws) + keys_offset(N));
-  const float thr2 = prm->ransac_thr * prm->ransac_thr;
-  ST_CHECK_HIP(hipMemsetAsync(keys, 0, (size_t)N * sizeof(unsigned long long), s));
-  hipLaunchKernelGGL(cmc_fit_score_kernel, dim3(kFitParts, N), dim3(256), 0, s, mesh, P, thr2, keys);
-  hipLaunchKernelGGL(cmc_fit_kernel, dim3(N), dim3(256), 0, s, mesh, P, thr2, prm->min_inlier_ratio, keys,
-                     warps_out_dev, inliers_out_dev);
-  ST_CHECK_HIP(hipGetLastError());
-  return ST_OK;
+  hipLaunchKernelGGL(cmc_load_flow_kernel, dim3((unsigned)((2LL * kPlane + 255) / 256), N), dim3(256), 0, s, g, flow_dev,
+                     static_cast<float*>(ws));
+  return launch_mesh_fit(N, img_h, img_w, prm, ws, warps_out_dev, mesh_out_dev, inliers_out_dev, s);
+}
+
+extern "C" int st_cmc_fit(const float* points_dev, int N, int P, float ransac_thr, float min_inlier_ratio, void* ws,
+                          size_t ws_bytes, float* warps_out_dev, unsigned char* inliers_out_dev, st_stream_t stream) {
+  using namespace st;
+  ST_REQUIRE(points_dev && warps_out_dev && ws && N > 0, "st_cmc_fit: bad argument");
+  ST_REQUIRE(P >= 2 && P <= kMaxPoints, "st_cmc_fit: %d points, must be in 2..%d", P, kMaxPoints);
+  ST_REQUIRE(ws_bytes >= st_cmc_workspace_bytes(N), "st_cmc_fit: workspace %zu < %zu bytes", ws_bytes,
+             st_cmc_workspace_bytes(N));
+  return launch_fit(points_dev, N, P, ransac_thr, min_inlier_ratio, ws, warps_out_dev, inliers_out_dev,
+                    static_cast<hipStream_t>(stream));
 }

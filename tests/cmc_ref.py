@@ -213,19 +213,21 @@ def update_matrices(R0, R1, flow, dt):
                     -1).astype(dt)
 
 
-def box_solve(M, m, dt):
+def box_solve(M, m, dt, reverse=False):
+    """reverse: the box sums accumulated from the far end (the same sums in another rounding order)."""
     h, w = M.shape[:2]
+    order = range(2 * m, -1, -1) if reverse else range(2 * m + 1)
     P = np.pad(M, ((m, m), (0, 0), (0, 0)), mode='edge')
-    V = sum(P[d:d + h] for d in range(2 * m + 1))
+    V = sum(P[d:d + h] for d in order)
     P = np.pad(V, ((0, 0), (m, m), (0, 0)), mode='edge')
-    S = sum(P[:, d:d + w] for d in range(2 * m + 1)).astype(dt)
+    S = sum(P[:, d:d + w] for d in order).astype(dt)
     S = S * dt(1.0 / ((2 * m + 1) ** 2))
     g11, g12, g22, h1, h2 = (S[..., i] for i in range(5))
     idet = dt(1) / (g11 * g22 - g12 * g12 + dt(1e-3))
     return np.stack([(g11 * h2 - g12 * h1) * idet, (g22 * h1 - g12 * h2) * idet], -1).astype(dt)
 
 
-def farneback(prev, curr, winsize=31, dtype=np.float64, per_level=False):
+def farneback(prev, curr, winsize=31, dtype=np.float64, per_level=False, reverse_box=False):
     """Dense flow prev -> curr (uint8 255 x 255 planes) -> (255, 255, 2) in dtype (per_level: every level, finest first)."""
     dt = np.dtype(dtype).type
     lv = levels()
@@ -242,7 +244,7 @@ def farneback(prev, curr, winsize=31, dtype=np.float64, per_level=False):
             flow = (resize_f(flow, side, side, dt) * dt(2.0)).astype(dt)
         M = update_matrices(R[k][0], R[k][1], flow, dt)
         for it in range(3):
-            flow = box_solve(M, m, dt)
+            flow = box_solve(M, m, dt, reverse_box)
             if it < 2:
                 M = update_matrices(R[k][0], R[k][1], flow, dt)
         out.insert(0, flow)
@@ -262,9 +264,10 @@ def mesh(flow, img_h, img_w, step=16):
     return src, (src + med).astype(np.float32)
 
 
-def consensus_fit(src, dst, thr=5.0, min_ratio=0.3, dtype=np.float32):
+def consensus_fit(src, dst, thr=5.0, min_ratio=0.3, dtype=np.float32, with_winner=False):
     """Every two-point similarity (i < j), largest inlier set (squared residual <= thr^2; ties: lowest (i, j)), linear
-    least-squares refit of [a -b tx; b a ty] over it.  -> (warp (2, 3) float32 or None, ratio, inliers bool (P,))."""
+    least-squares refit of [a -b tx; b a ty] over it.  -> (warp (2, 3) float32 or None, ratio, inliers bool (P,));
+    with_winner: also the winning hypothesis (i, j, its residuals in dtype), None when no hypothesis is usable."""
     dt = np.dtype(dtype).type
     p, q = src.astype(dt), dst.astype(dt)
     P = len(p)
@@ -287,13 +290,15 @@ def consensus_fit(src, dst, thr=5.0, min_ratio=0.3, dtype=np.float32):
     counts[~ok] = 0
     h = int(np.argmax(counts))
     if counts[h] == 0:
-        return None, 0.0, np.zeros(P, bool)
+        res = (None, 0.0, np.zeros(P, bool))
+        return res + (None,) if with_winner else res
     ex = a[h] * p[:, 0] - b[h] * p[:, 1] + tx[h] - q[:, 0]
     ey = b[h] * p[:, 0] + a[h] * p[:, 1] + ty[h] - q[:, 1]
     inl = (ex * ex + ey * ey) <= thr2
     warp = lsq_similarity(src[inl], dst[inl])
     ratio = float(inl.sum()) / P
-    return (warp if ratio >= min_ratio else None), ratio, inl
+    res = ((warp if ratio >= min_ratio else None), ratio, inl)
+    return res + ((int(i[h]), int(j[h]), np.sqrt(ex * ex + ey * ey)),) if with_winner else res
 
 
 def lsq_similarity(src, dst):

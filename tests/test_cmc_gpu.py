@@ -69,6 +69,10 @@ def test_mesh_and_fit_vs_restatement(cuda):
     assert np.array_equal(mesh[:, 0:2], src) and np.array_equal(mesh[:, 2:4], dst)
     warp, ratio, rinl = R.consensus_fit(src, dst, 5.0, 0.3, np.float32)
     res = R.residuals(src, dst, R.lsq_similarity(src[rinl], dst[rinl]))
+    # whatever the flags: the warp is the least-squares refit over the device's own inlier set, the ratio its size
+    own = R.lsq_similarity(src[inl], dst[inl])
+    np.testing.assert_allclose(row[2:].reshape(2, 3), own, rtol=1e-4, atol=1e-4 * np.abs(own).max())
+    assert row[1] == np.float32(inl.sum()) / np.float32(len(inl)) and row[0] == (1.0 if row[1] >= np.float32(0.3) else 0.0)
     differ = inl != rinl
     if differ.any():     # only points whose residual sits on the threshold may differ
         assert np.all(np.abs(res[differ] - 5.0) <= 1e-3 + 1e-3 * 5), f'{differ.sum()} inlier flags differ'

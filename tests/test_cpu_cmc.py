@@ -340,3 +340,117 @@ def test_farneback_recovers_known_camera_motion(A, moving):
     warp, ratio, _, _, _ = R.estimate(p0, p1, h, w, dtype=np.float32)
     assert warp is not None and ratio > (0.5 if moving else 0.9)
     assert _corner_error(warp, A) <= (CORNER_TOL_MOVING if moving else CORNER_TOL)
+
+
+# ---- the scenarios of tests/test_cmc_kernels_gpu.py: preconditions, from the restatement alone --------------------------
+import cmc_cases as K  # noqa: E402
+
+
+@pytest.mark.parametrize('geometry', K.GEOMETRIES, ids=K.geometry_id)
+def test_front_cases_equalise_to_two_grey_levels(geometry):
+    """A frame whose plane is constant cannot tell a wrong resize or LUT from a right one: every non-constant front
+    case yields at least 2 grey levels, through the uint8 frame and through the padded fp32 canvas alike."""
+    fh, fw, h, w = geometry
+    for kind in K.FRONT_KINDS:
+        f = K.front_frame(kind, geometry)
+        plane = R.front(f, h, w)
+        assert plane.shape == (255, 255) and plane.dtype == np.uint8
+        assert np.array_equal(R.front(K.canvas_f32(f, h, w), h, w), plane)
+        levels = len(np.unique(plane))
+        assert levels == 1 if kind == 'constant' else levels >= 2, (kind, levels)
+    if h * w > 255 * 255:     # down-scaling: the one differing pixel stays one plane pixel, the extreme of equalizeHist
+        assert (R.front(K.front_frame('one-off', geometry), h, w) != 0).sum() <= 4
+    o = K.out_of_range_f32(geometry)
+    assert o.min() == -7 and o.max() == 300 and len(np.unique(R.front(o, h, w))) >= 2 or h * w < 8
+
+
+def test_front_batch_crosses_the_chunk():
+    assert K.FRONT_BATCH > 32
+    fh, fw, h, w = K.FRONT_BATCH_GEOMETRY
+    planes = [R.front(K.front_frame('random', K.FRONT_BATCH_GEOMETRY, seed=i), h, w) for i in range(K.FRONT_BATCH)]
+    # no two planes alike: a plane written to the wrong slot cannot pass for the right one
+    assert len({p.tobytes() for p in planes}) == K.FRONT_BATCH
+
+
+@pytest.mark.parametrize('name', list(K.FIT_CASES))
+def test_fit_cases_do_not_depend_on_rounding(name):
+    """float32 restatement == float64 restatement in winner, inlier set and ratio; under the float64 winner no residual
+    lies within 1e-3 thr of thr, but the ones a case puts exactly on it; and what each case was built to show."""
+    c = K.fit_case(name)
+    P, thr = len(c['points']), c['thr']
+    assert 2 <= P <= 1024
+    w32, r32, i32, win32 = K.fit_reference(name, np.float32)
+    w64, r64, i64, win64 = K.fit_reference(name, np.float64)
+    assert np.array_equal(i32, i64) and r32 == r64 and (w32 is None) == (w64 is None)
+    assert (win32 is None) == (win64 is None)
+    if win64 is not None:
+        assert win32[:2] == win64[:2], 'winning hypothesis differs between float32 and float64'
+        free = np.ones(P, bool)
+        free[list(c['on_threshold'])] = False
+        assert np.abs(win64[2][free] - thr).min() > 1e-3 * thr
+        for k in c['on_threshold']:
+            assert win64[2][k] == thr and win32[2][k] == np.float32(thr)
+    if 'winner' in c:
+        assert win32[:2] == c['winner']
+    if 'n_inliers' in c:
+        assert int(i32.sum()) == c['n_inliers']
+    if 'valid' in c:
+        assert (w32 is not None) == c['valid']
+        # the device decides in float32
+        assert (np.float32(i32.sum()) / np.float32(P) >= np.float32(c['min_ratio'])) == c['valid']
+    if 'outliers' in c:
+        assert not i32[c['outliers']].any() and int(i32.sum()) == P - len(c['outliers'])
+        assert np.all(R.residuals(c['points'][:, :2], c['points'][:, 2:], K.MOTION)[c['outliers']] >= 10 * thr)
+    for k in c.get('inlier', ()):
+        assert i32[k]
+    for k in c.get('outlier', ()):
+        assert not i32[k]
+    if 'motion' in c:
+        np.testing.assert_allclose(w32, c['motion'], rtol=1e-3, atol=0)      # a, b, tx, ty each to 1e-3 of itself
+    if 'base_points' in c:       # (e): the repeated sources add den == 0 hypotheses and change nothing
+        n = c['base_points']
+        p = c['points']
+        d = p[:, None, :2] - p[None, :, :2]
+        assert ((d ** 2).sum(-1) == 0).sum() > P, 'no coincident source points'
+        wb, rb, ib, winb = R.consensus_fit(p[:n, :2], p[:n, 2:], thr, c['min_ratio'], np.float32, with_winner=True)
+        assert winb[:2] == win32[:2] and np.array_equal(ib, i32[:n]) and not i32[n:].any()
+        assert np.array_equal(wb, w32)
+
+
+def test_ratio_boundary_in_float32():
+    assert np.float32(120) / np.float32(400) >= np.float32(0.3)
+    assert not np.float32(119) / np.float32(400) >= np.float32(0.3)
+    assert K.fit_reference('g120')[0] is not None and K.fit_reference('g119')[0] is None
+
+
+def test_fit_batches_share_a_point_count():
+    for names in K.FIT_BATCHES.values():
+        assert len(names) == 5 and len({len(K.fit_case(n)['points']) for n in names}) == 1
+        assert names[0] == names[4]       # the same set twice: its two rows must agree, whatever the keys held between
+
+
+def test_mesh_fields_hold_ties_and_odd_cells():
+    f = K.flow_fields()
+    assert {s * s % 2 for s in K.MESH_STEPS} == {0, 1}
+    assert sorted(255 // s for s in K.MESH_STEPS)[0] == 15 and sorted(255 // s for s in K.MESH_STEPS)[-1] == 31
+    assert np.signbit(f['neg-zero']).any() and not np.signbit(f['neg-zero']).all() and not f['neg-zero'].any()
+    for s in K.MESH_STEPS:
+        cell = f['two-valued'][:s, :s]
+        for c in range(2):
+            v, n = np.unique(cell[..., c], return_counts=True)
+            assert len(v) == 2 and abs(int(n[0]) - int(n[1])) == (s * s) % 2
+        src, dst = R.mesh(f['two-valued'], 255, 255, s)
+        want = (0.25, 1.5) if s % 2 == 0 else None     # even count: the mean of the two values
+        if want:
+            assert np.all(dst[:, 0] - src[:, 0] == np.float32(want[0])) and np.all(dst[:, 1] - src[:, 1] == want[1])
+    assert len(np.unique(f['noise'])) > 0.99 * f['noise'].size
+
+
+def test_options_scene_is_recovered_by_the_restatement():
+    """The glme overrides the end-to-end GPU test uses (step 8, winsize 15, thr 3, ratio 0.5) recover the known motion
+    in the float32 restatement within the tolerance of the default options."""
+    A, moving = K.FLOW_SCENES[K.OPTIONS_SCENE]
+    p0, p1 = K.scene_planes(K.OPTIONS_SCENE)
+    warp, ratio, src, _, _ = R.estimate(p0, p1, K.IMG_H, K.IMG_W, dtype=np.float32, **K.OPTIONS)
+    assert len(src) == 961 and warp is not None and ratio >= 0.9
+    assert _corner_error(warp, A) <= CORNER_TOL
