@@ -218,20 +218,27 @@ DEFAULTS = dict(num_disparities=48, block_size=3, P1=96, P2=384, disp12_max_diff
                 speckle_window_size=400, speckle_range=10, pre_filter_cap=63, color=True)
 
 
-def sgbm(left, right, stages=False, **kw):
-    """uint8 (3, h, w) BGR left / right -> int16 (h, w) disparity x 16 (-16 invalid).  stages=True: a dict with the
-    block-summed cost 'cost' (h, w - D, D), 'raw' (before the median), 'median' and 'final'."""
+def aggregate(left, right, **kw):
+    """uint8 (3, h, w) BGR left / right -> int64 (block-summed cost C, aggregated cost S), both (h, w - D, D)
+    (rules 1 - 4).  tests/test_cpu_sgbm.py counts the tied minima of S with it."""
     p = dict(DEFAULTS, **kw)
-    D = p['num_disparities']
     ft = ftzero_of(p['pre_filter_cap'])
     if p['color']:
         cn, l, r = 3, left, right
     else:
         cn, l, r = 1, to_grey(left), to_grey(right)
-    w = l.shape[-1]
     PL, PR = prefilter(l, ft), prefilter(r, ft)
-    C = block_sum(pixel_cost(PL, PR, D, cn), p['block_size'])
-    S = paths(C, p['P1'], p['P2'])
+    C = block_sum(pixel_cost(PL, PR, p['num_disparities'], cn), p['block_size'])
+    return C, paths(C, p['P1'], p['P2'])
+
+
+def sgbm(left, right, stages=False, **kw):
+    """uint8 (3, h, w) BGR left / right -> int16 (h, w) disparity x 16 (-16 invalid).  stages=True: a dict with the
+    block-summed cost 'cost' (h, w - D, D), 'raw' (before the median), 'median' and 'final'."""
+    p = dict(DEFAULTS, **kw)
+    D = p['num_disparities']
+    w = left.shape[-1]
+    C, S = aggregate(left, right, **kw)
     raw = decide(S, D, w, p['uniqueness_ratio'], p['disp12_max_diff'])
     med = median3(raw)
     fin = speckles(med, p['speckle_window_size'], 16 * p['speckle_range'])

@@ -226,3 +226,120 @@ def test_grey_mode_matches_on_the_bgr2gray_plane():
                 num_disparities=32)
     assert np.array_equal(g, g3)                           # grey of a grey BGR image is the image itself
     assert (g > 0).mean() > 0.3
+
+
+# ---- preconditions of the scenarios of tests/sgbm_cases.py (run on the device by tests/test_sgbm_edges_gpu.py) -----------
+import sgbm_cases as K  # noqa: E402
+
+
+def _computed(m, D):
+    return m[:, D:]
+
+
+@pytest.mark.parametrize('D', K.TIES_D)
+@pytest.mark.parametrize('name', K.TIES_TIED)
+def test_ties_scenarios_tie_and_are_decided(name, D):
+    """The tied scenarios have two or more minima of S at half of the computed pixels or more (measured at D 48:
+    const63, stripes-rolled, period3, inverse 1.00, halfplane-rolled 0.61; halfplane-rolled gives 0.42 at D 16 and 0.79
+    at D 64, every other one 1.00 at each D), and at uniqueness_ratio 0 the restatement decides more than half of those
+    pixels (measured: all of them), so 'the lowest d wins' shows in the map."""
+    left, right = K.TIES[name]
+    _, S = R.aggregate(left, right, **K.ties_kw(D, 0))
+    tied = K.tied_minima(S)
+    assert tied.mean() >= (0.5 if D >= 48 or name != 'halfplane-rolled' else 0.4), f'tied share {tied.mean():.2f}'
+    raw = _computed(R.decide(S, D, left.shape[-1], 0, 0), D)
+    assert (raw[tied] != R.INVALID).mean() > 0.5
+    assert np.array_equal(raw, _computed(K.reference(left, right, K.ties_kw(D, 0))['raw'], D))
+
+
+def test_ties_scenarios_hold_disp2_ties():
+    """Two unique pixels of one row claim the same x - best at the same minS with different best, so 'ties go to the
+    highest x' decides the entry: stripes-rolled has 24 such entries at uniqueness_ratio 0 (D 16, 48 and 64)."""
+    left, right = K.TIES['stripes-rolled']
+    for D in K.TIES_D:
+        _, S = R.aggregate(left, right, **K.ties_kw(D, 0))
+        assert K.disp2_ties(S, D, 0) == 24
+    # what the textured pairs of tests/test_sgbm_gpu.py lack is the tied minimum of S: none at this size
+    a, b = K.texture_pair(5, *K.TIES_HW, 48)
+    assert not K.tied_minima(R.aggregate(a, b)[1]).any()
+
+
+def test_geometry_scenarios_have_structure():
+    """Every geometry has a non-constant block-summed cost, and in at least six of the nine the map before the median
+    has valid and invalid computed pixels or more than one level (w = D + 1 leaves one column: 1 x 17 and 5 x 65 decide
+    one level)."""
+    rich = 0
+    for g in K.GEOMETRY:
+        h, w, D = g[:3]
+        left, right = K.geometry_pairs(g)[0]
+        assert left.shape == (3, h, w)
+        st = K.reference(left, right, K.geometry_kw(g))
+        assert st['cost'].shape == (h, w - D, D) and len(np.unique(st['cost'])) > 1, K.geometry_id(g)
+        rich += len(np.unique(_computed(st['raw'], D))) > 1
+    assert rich >= 6
+    assert len(K.GEOMETRY) == 9 and any((g[1] - g[2]) % 4 and (g[1] - g[2]) % 16 for g in K.GEOMETRY)
+
+
+@pytest.mark.parametrize('kw', K.OPTIONS, ids=K.options_id)
+def test_each_option_reaches_the_final_map(kw):
+    left, right = K.options_pairs()[0]
+    base = K.reference(left, right, {})['final']
+    fin = K.reference(left, right, kw)['final']
+    assert (base > 0).mean() > 0.3
+    if kw in K.OPTIONS_SAME_AS_DEFAULT:
+        # rule 6: disp12_max_diff <= 0 is 1, as the default 0 is; the check itself acts on this pair (1000 differs)
+        assert np.array_equal(fin, base)
+        assert not np.array_equal(K.reference(left, right, dict(disp12_max_diff=1000))['final'], base)
+    else:
+        assert (fin != base).any()
+
+
+def test_bound_scenario_passes_the_top_bit_of_int16():
+    """P2 = 5819 is the largest the constructor admits with the default block and cap; on unmatched binary noise S
+    reaches 23035 >= 2^14 (and stays below 2^15), so a value that lost its top bit or its sign would show."""
+    from stereotracking_amd.sgbm import StereoSGBM
+    StereoSGBM(**K.BOUND_KW)
+    with pytest.raises(ValueError, match='int16'):
+        StereoSGBM(P2=K.BOUND_KW['P2'] + 4)
+    left, right = K.bound_pairs()[0]
+    _, S = R.aggregate(left, right, **K.BOUND_KW)
+    assert S.max() == 23035 and 16384 <= S.max() <= 32767
+    raw = _computed(K.reference(left, right, K.BOUND_KW)['raw'], 48)
+    assert 0.2 < (raw != R.INVALID).mean() < 0.8
+
+
+def test_speckle_scenarios_are_what_they_claim():
+    kept = lambda name, wd, rg=10: int((K.speckle_reference(K.SPECKLE[name], wd, rg) != R.INVALID).sum())  # noqa: E731
+    n = K.SERPENTINE_PIXELS
+    assert (K.SPECKLE['serpentine'] != R.INVALID).sum() == n == (K.SPECKLE['serpentine-rising'] != R.INVALID).sum()
+    for name in ('serpentine', 'serpentine-rising'):       # one component: whole at 400, gone at 900
+        assert kept(name, 400) == n and kept(name, 900) == 0
+    assert kept('serpentine-rising', 1, 0) == n - 16       # range 0: the rows part, the joining pixels go at window 1
+    assert kept('checkerboard', 1) == 0 and kept('checkerboard', 0) == 32 * 48
+    assert np.array_equal(K.speckle_reference(K.SPECKLE['checkerboard'], 0, 10), K.SPECKLE['checkerboard'])
+    assert kept('constant', 900) == 32 * 48 and kept('constant', 32 * 48) == 0
+    # the batch: each map alone loses everything at 400 (components of 192, 240 and 350 pixels); an edge across a seam,
+    # in the last row or from the last pixel to the next map's first, would keep the 192 + 240 on both sides of it
+    maps = K.SPECKLE['batch3']
+    assert maps.shape[0] == 3 and all(maps[n, -1, -1] == maps[n + 1, 0, 0] for n in range(2))
+    assert all((maps[n, -1] == maps[n + 1, 0]).all() for n in range(2))
+    assert kept('batch3', 400) == 0 and kept('batch3', 1) == (maps != R.INVALID).sum()
+    for joined in (maps.reshape(-1, 48), maps.reshape(1, -1)):      # stacked rows; one long row
+        out = R.speckles(joined.astype(np.int64), 400, 160)
+        assert (out != R.INVALID).sum() == 2 * 432
+
+
+def test_median_scenarios_hold_ties_and_invalid():
+    for hw in K.MEDIAN_HW:
+        m = K.median_maps(hw)
+        assert m.shape == (3,) + hw and m.dtype == np.int16
+    m = K.median_maps((2, 300))
+    assert (m == R.INVALID).any() and len(np.unique(m)) < 8
+    assert any(not np.array_equal(R.median3(a), a) for a in m)
+
+
+def test_dirty_workspace_scenarios_are_opposites():
+    """noise-shift9 is valid at every computed pixel, const63 at none (defaults)."""
+    a = K.reference(*K.TIES[K.DIRTY[0]], {})['final']
+    b = K.reference(*K.TIES[K.DIRTY[1]], {})['final']
+    assert (_computed(a, 48) != R.INVALID).mean() > 0.9 and (b == R.INVALID).all()

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import sgbm_ref as R
+from sgbm_check import assert_stages_bit_exact, batch as _batch, up as _up
 
 pytestmark = pytest.mark.gpu
 
@@ -13,17 +14,6 @@ def _pairs(N, h, w, D, seed=0):
     from stereotracking_amd.synthetic import synthetic_stereo_pair
     ps = [synthetic_stereo_pair(seed + i, h, w, max_disp=D) for i in range(N)]
     return [p['left'] for p in ps], [p['right'] for p in ps]
-
-
-def _batch(frames, H, W, cuda, pad=114.0):
-    out = np.full((len(frames), 3, H, W), pad, np.float32)
-    for i, f in enumerate(frames):
-        out[i, :, :f.shape[1], :f.shape[2]] = f
-    return torch.from_numpy(out).to(cuda)
-
-
-def _up(v, d=32):
-    return (v + d - 1) // d * d
 
 
 CASES = [  # N, h, w, module kwargs
@@ -37,27 +27,8 @@ CASES = [  # N, h, w, module kwargs
 
 @pytest.mark.parametrize('N,h,w,kw', CASES)
 def test_stages_bit_exact(cuda, N, h, w, kw):
-    from stereotracking_amd.sgbm import StereoSGBM
-    m = StereoSGBM(**kw)
-    L, Rt = _pairs(N, h, w, m.num_disparities, seed=N * 7 + h)
-    H, W = _up(h), _up(w)
-    lb, rb = _batch(L, H, W, cuda), _batch(Rt, H, W, cuda)
-    refs = [R.sgbm(a, b, stages=True, **kw) for a, b in zip(L, Rt)]
-    cost, raw = m.match(lb, rb, (h, w))
-    med_gpu = m.median(raw)
-    med_ref_in = m.median(torch.from_numpy(np.stack([r['raw'] for r in refs])).to(cuda))
-    fin, status = m.speckle(torch.from_numpy(np.stack([r['median'] for r in refs])).to(cuda))
-    out = torch.full((N, 3, H, W), -1.0, device=cuda)
-    m.compute(lb, rb, (h, w), out)
-    torch.cuda.synchronize()
-    for i, r in enumerate(refs):
-        assert np.array_equal(cost[i].cpu().numpy(), r['cost']), f'pair {i}: cost'
-        assert np.array_equal(raw[i].cpu().numpy(), r['raw']), f'pair {i}: map before the median'
-        assert np.array_equal(med_gpu[i].cpu().numpy(), r['median']), f'pair {i}: median of the GPU map'
-        assert np.array_equal(med_ref_in[i].cpu().numpy(), r['median']), f'pair {i}: median'
-        assert np.array_equal(fin[i].cpu().numpy(), r['final']), f'pair {i}: speckle filter'
-        assert np.array_equal(out[i].cpu().numpy(), R.disp_postp(r['final'], H, W)), f'pair {i}: disp_postp'
-    assert int(status.item()) == 0 and int(m.last_status.item()) == 0, 'speckle union-find did not converge'
+    L, Rt = _pairs(N, h, w, kw.get('num_disparities', 48), seed=N * 7 + h)
+    refs, _ = assert_stages_bit_exact(cuda, L, Rt, kw)
     valid = np.mean([(r['final'] > 0).mean() for r in refs])
     assert valid > 0.3, f'scenario has too few valid pixels ({valid:.2f}) to test anything'
 
