@@ -659,12 +659,16 @@ int st_tracker_track_records_cmc(StTracker* t, const int* frame_ids, const float
  *            matches the fixed-point BGR2GRAY of the frames.  Both forms give the same bits.
  *   output   disp_postp (N, 3, H, W) fp32 = max(d16, 0) / 16 in all three channels, 0 outside h x w (the PNG
  *            loader's convention: invalid -> 0).
- *   limits   min_disparity 0; num_disparities in {16, 32, 48, 64} and < w; w <= 4096; block_size odd, 1..9;
+ *   limits   min_disparity 0; num_disparities in {16, 32, 48, 64} (one level per lane of a wave) or {128, 192, 256}
+ *            (2, 3, 4 levels per lane) and < w; every other value is refused (ST_ERR_INVALID); w <= 4096; N h w < 2^31;
+ *            block_size odd, 1..9;
  *            pre_filter_cap 1..127; parameter sets whose worst-case aggregated cost
  *            3 (block_size^2 cn (2 ftzero + 63) + max(P2, P1 + 1)) leaves int16 are refused (ST_ERR_INVALID).
  *   status   int on the device, written by every call that runs the speckle filter: 0 = every union-find loop
  *            converged; bit 0 / 1 = a find / link loop reached its bound (the result is then not the spec's).
- *   ws: caller-owned device workspace of st_sgbm_workspace_bytes(N, h, w, D).  Enqueued on `stream`, no host sync.
+ *   ws: caller-owned device workspace of st_sgbm_workspace_bytes(N, h, w, D), 8-byte aligned; the two int16 cost
+ *   volumes in it take 2 N h (w - D) D bytes each, so the size passes 2^32 for large batches at D = 256 (size_t
+ *   throughout).  Enqueued on `stream`, no host sync.
  *   Stage entry points (tests): st_sgbm_match_f32 -> the block-summed cost C (N, h, w - D, D) int16 and / or the int16
  *   disparity x 16 (N, h, w) after the left-right check, before the median (-16 invalid); st_sgbm_median (3 x 3,
  *   replicated borders); st_sgbm_speckle (filterSpeckles with newVal -16; out int16 and / or disp_postp, workspace
@@ -672,7 +676,7 @@ int st_tracker_track_records_cmc(StTracker* t, const int* frame_ids, const float
  * ---------------------------------------------------------------------- */
 typedef struct StSgbmParams {
   int struct_size;         /* sizeof(StSgbmParams) */
-  int num_disparities;     /* D: 16, 32, 48 or 64 */
+  int num_disparities;     /* D: 16, 32, 48, 64, 128, 192 or 256 */
   int block_size;          /* odd */
   int P1, P2;              /* smoothness penalties; P2 is used as max(P2, P1 + 1) */
   int disp12_max_diff;     /* <= 0 is taken as 1 */

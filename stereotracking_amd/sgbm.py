@@ -20,6 +20,7 @@ from .engine import RawChunk, _require_cuda
 from .registry import MODELS
 
 INT16_MAX = 32767
+NUM_DISPARITIES = (16, 32, 48, 64, 128, 192, 256)
 
 
 def ftzero_of(pre_filter_cap):
@@ -28,7 +29,10 @@ def ftzero_of(pre_filter_cap):
 
 @MODELS.register_module()
 class StereoSGBM(nn.Module):
-    """Launcher with no parameters and no CPU forward.  compute() fills a (N, 3, H, W) disp_postp from N pairs."""
+    """Launcher with no parameters and no CPU forward.  compute() fills a (N, 3, H, W) disp_postp from N pairs.
+
+    num_disparities: 16, 32, 48 or 64 (one level per lane of a wave) or 128, 192 or 256 (2, 3 or 4 levels per lane; the
+    two cost volumes take 2 * 2 * N * h * (w - D) * D bytes of the workspace).  min_disparity is 0 and the mode SGBM_3WAY."""
 
     def __init__(self, min_disparity=0, num_disparities=48, block_size=3, P1=96, P2=384, disp12_max_diff=0,
                  uniqueness_ratio=10, speckle_window_size=400, speckle_range=10, pre_filter_cap=63, mode='SGBM_3WAY',
@@ -38,9 +42,9 @@ class StereoSGBM(nn.Module):
             raise NotImplementedError(f"StereoSGBM: only mode='SGBM_3WAY' is implemented (got {mode!r})")
         if min_disparity != 0:
             raise NotImplementedError(f'StereoSGBM: only min_disparity=0 is implemented (got {min_disparity})')
-        if num_disparities not in (16, 32, 48, 64):
-            raise ValueError(f'StereoSGBM: num_disparities must be 16, 32, 48 or 64 (one level per lane of a wave), '
-                             f'got {num_disparities}')
+        if num_disparities not in NUM_DISPARITIES:
+            raise ValueError(f'StereoSGBM: num_disparities must be 16, 32, 48 or 64 (one level per lane of a wave) or '
+                             f'128, 192 or 256 (whole 64-level slots: 2, 3 or 4 levels per lane), got {num_disparities}')
         if block_size < 1 or block_size % 2 != 1:
             raise ValueError(f'StereoSGBM: block_size must be odd and >= 1, got {block_size}')
         if not 1 <= pre_filter_cap <= 127:
