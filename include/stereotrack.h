@@ -445,6 +445,28 @@ int st_disp_upsample_pack(const float* disp_lr_dev, int N, int Hf, int Wf, int s
                           int W, int valid_h, int valid_w, float* disp_postp_dev,
                           st_stream_t stream);
 
+/* LEFT-RIGHT CHECK of the stereo module (StereoCostVolume(lr_check=True); csrc/lr_check.hip).  NEW, no reference function
+ * (as for the module itself); the consumer contract is the one above: 0 = invalid in disp_postp
+ * (loading_disparity.py:85-86,129-134; extract_depth keeps 0 < depth < 150, ocsort_disparity.py:136-175).  Levels are the
+ * unit; s = `scale` is the level spacing in image pixels.  With V [N][H][W][D] the volume st_softargmin reads:
+ *   1  dL = st_softargmin(V)
+ *   2  VR[n][y][x'][d] = V[n][y][x'+d][d] if x'+d < W, else 0
+ *   3  dR = softargmin(VR) in the operation order of oracle_softargmin (maximum first, then d ascending)
+ *   4  r = (int)floorf(dL + 0.5f), xr = x - r; (y, x) is invalid if dL is not finite, xr < 0 (or xr >= W), or
+ *      !(fabsf(dL - dR[y][xr]) * (float)s <= lr_max_diff)   (NaN fails; a difference equal to lr_max_diff is valid)
+ *   5  disp_postp[n][c][Y][X] = valid(Y / s, X / s) ? the value st_disp_upsample_pack writes : +0;
+ *      disp_mask[n][0][Y][X] = valid ? 1 : 0 inside (valid_h, valid_w), 0 outside.
+ * st_softargmin_right: rules 2 + 3 -> out_disp_right_dev [N][H][W] (levels).  Any D >= 1 (16-byte loads when D % 4 == 0
+ * and vol_dev is 16-byte aligned), any W >= 1 (W < D included), bit-equal to oracle_softargmin on the sheared volume. */
+int st_softargmin_right(const float* vol_dev, int N, int H, int W, int D, float temperature,
+                        float* out_disp_right_dev, st_stream_t stream);
+/* st_lr_check_pack: rules 4 + 5 in one pass.  disp_left_dev / disp_right_dev [N][Hl][Wl] (levels), H == Hl * scale,
+ * W == Wl * scale, lr_max_diff >= 0 in image pixels; disp_postp_dev [N][3][H][W], disp_mask_dev [N][1][H][W] or NULL.
+ * A valid pixel's disparity is bit-identical to st_disp_upsample_pack's on the same disp_left. */
+int st_lr_check_pack(const float* disp_left_dev, const float* disp_right_dev, int N, int Hl, int Wl, int scale, int H,
+                     int W, int valid_h, int valid_w, float lr_max_diff, float* disp_postp_dev, float* disp_mask_dev,
+                     st_stream_t stream);
+
 /* Bilinear x`scale` upsampling (align_corners=False) of an NHWC feature map [N][Hf][Wf][C] (pixel stride feat_ld floats)
  * to [N][Hf*scale][Wf*scale][C] dense: the feature side of the stereo module's FULL-RESOLUTION mode
  * (StereoCostVolume(full_res=True): the D = max_disp level volume of north_star's sizing, D x H x W, built at image

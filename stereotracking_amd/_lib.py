@@ -197,6 +197,8 @@ _PROTOS = {
     'st_costvolume_softargmin': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     'st_softargmin': (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp]),
     'st_disp_upsample_pack': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'st_softargmin_right': (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    'st_lr_check_pack': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     'st_feat_upsample': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'st_costvolume_agg3d_supported': (_i, [_i, _i]),
     'st_costvolume_agg3d': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _i, _vp, _vp]),

@@ -409,7 +409,9 @@ class OCSORT_Disparity(nn.Module):
                 rgb_only=getattr(det, 'rgb_only', False),
                 full_res=bool(getattr(sm, 'full_res', False)) if stereo else False,
                 full_res_channels=(sm.reduce.out_channels if stereo and getattr(sm, 'full_res', False) else 8),
-                sgbm=sgbm, depth_method=self.depth_extraction)
+                sgbm=sgbm, depth_method=self.depth_extraction,
+                lr_check=bool(getattr(sm, 'lr_check', False)) if stereo else False,
+                lr_max_diff=getattr(sm, 'lr_max_diff', 1.0) if stereo else 1.0)
             for p in runner.pipes:     # the track-box depth reads run k's disparity while later runs are in flight
                 p.disp_buffers = self.queue_depth + 1
             ent = self._dense[key] = [runner, None]

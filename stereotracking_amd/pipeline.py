@@ -106,7 +106,7 @@ class StereoDensePipeline:
                  stereo=True, max_disp=192, feat_stride=4, temperature=32.0, score_thr=0.01, iou_thr=0.5,
                  max_det=1000, baseline=0.25, focal_length=640, pad_size_divisor=32, agg_layers=0, agg3d_layers=0,
                  split_bf16=None, multi_label=True, rgb_only=False, full_res=False, full_res_channels=8, sgbm=None,
-                 depth_method='reference'):
+                 depth_method='reference', lr_check=False, lr_max_diff=1.0):
         """max_det: rows of the fixed-size detection buffer per frame.  The reference applies NO cap on the
         kept boxes (yolox_style=True => max_per_img = len(results)), so this is a
         capacity, not a threshold: `run()` reports `overflow` whenever a frame kept more boxes than fit, and
@@ -118,7 +118,10 @@ class StereoDensePipeline:
         (stereo must be False) on img + that disparity - the configuration the reference's detector was trained in.
 
         depth_method: the per-box depth estimator of box_depth() (DEPTH_METHODS; 'reference' = the reference's default
-        extract_depth, launched through st_box_depth exactly as before)."""
+        extract_depth, launched through st_box_depth exactly as before).
+
+        lr_check / lr_max_diff: the stereo module's left-right check (stereo.py): pixels that fail it are 0 in disp_postp -
+        so they drop out of the per-box depth - and `run()` also returns `disp_mask` (N,1,H,W), 1 = valid."""
         self.depth_method = str(depth_method)
         self._depth_code = depth_method_code(depth_method)
         self.lib = _lib.load()
@@ -143,7 +146,9 @@ class StereoDensePipeline:
         feat_channels = int(math.ceil(128 * widen_factor / 8) * 8)
         self.stereo_module = StereoCostVolume(max_disp, feat_stride, temperature, agg_layers if stereo else 0,
                                               agg3d_layers if stereo else 0, full_res=self.full_res,
-                                              full_res_channels=full_res_channels, feat_channels=feat_channels)
+                                              full_res_channels=full_res_channels, feat_channels=feat_channels,
+                                              lr_check=bool(lr_check) and bool(stereo), lr_max_diff=lr_max_diff)
+        self.lr_check, self.lr_max_diff = self.stereo_module.lr_check, self.stereo_module.lr_max_diff
         self.agg_layers = self.stereo_module.agg_layers
         self.agg3d_layers = self.stereo_module.agg3d_layers
         # split_bf16: the autotuner may pick the split-operand (bf16x3) conv instances (fp32 operands as three bf16 terms,
@@ -247,6 +252,9 @@ class StereoDensePipeline:
             # buffer i is rewritten)
             b['disp_ring'] = [torch.empty(N, 3, H, W, **f32) for _ in range(max(1, int(self.disp_buffers)))]
             b['disp_postp'] = b['disp_ring'][0]
+            # left-right check: one validity mask beside every disparity buffer (same slot, same guard event)
+            b['mask_ring'] = [torch.empty(N, 1, H, W, **f32) if self.lr_check else None for _ in b['disp_ring']]
+            b['disp_mask'] = b['mask_ring'][0]
             self.disp_guard = [None] * len(b['disp_ring'])
             self._disp_turn = 0
             b['depth'] = torch.empty(N, M, **f32)       # rows past the count are written as 0 by st_box_depth
@@ -270,10 +278,11 @@ class StereoDensePipeline:
             torch.cuda.current_stream(img.device).wait_event(self.disp_guard[k])
             self.disp_guard[k] = None
         out = b['disp_postp'] = b['disp_ring'][k]
+        mask = b['disp_mask'] = b['mask_ring'][k]
         if self.sgbm is not None:
             self.sgbm.compute(img, right, (self.ori_h, self.ori_w), out)
         else:
-            self.stereo_module.compute(self.det, img, right, (self.ori_h, self.ori_w), b['disp_lr'], out)
+            self.stereo_module.compute(self.det, img, right, (self.ori_h, self.ori_w), b['disp_lr'], out, disp_mask=mask)
         return out
 
     def box_depth(self, disp_postp, boxes, counts, out=None):
@@ -294,7 +303,7 @@ class StereoDensePipeline:
         may be engine.RawChunk (N uint8 frames each): the stem kernels cast + pad them while staging their windows.
         Returns a dict of device tensors (no host sync; the context's PERSISTENT buffers, overwritten by its next run): boxes (N,M,4) unscaled xyxy, scores, labels,
         prior_idx, counts (TRUE number kept per frame), overflow (N,) bool = counts > M, depth, scales,
-        scaled_boxes, disp_postp, head.  Rows past min(counts, M) are zero (prior_idx -1).  With disp_buffers > 1 the
+        scaled_boxes, disp_postp, head (and, with lr_check, disp_mask (N,1,H,W): 1 = valid).  Rows past min(counts, M) are zero (prior_idx -1).  With disp_buffers > 1 the
         stereo module's disp_postp is buffer `self.disp_slot` of the ring (see _buffers)."""
         if isinstance(img, RawChunk):
             if (self.stereo or self.sgbm is not None) and not isinstance(right, RawChunk):
@@ -320,9 +329,12 @@ class StereoDensePipeline:
             b['head'], self.score_thr, self.iou_thr, self.max_det, (self.ori_h, self.ori_w), out=b['decode'])
         depth, scales, sboxes = self.box_depth(disp_postp, boxes, counts)
         torch.gt(counts, self.max_det, out=b['overflow'])
-        return dict(boxes=boxes, scores=scores, labels=labels, prior_idx=prior, counts=counts,
-                    overflow=b['overflow'], depth=depth, scales=scales, scaled_boxes=sboxes,
-                    disp_postp=disp_postp, head=b['head'])
+        out = dict(boxes=boxes, scores=scores, labels=labels, prior_idx=prior, counts=counts,
+                   overflow=b['overflow'], depth=depth, scales=scales, scaled_boxes=sboxes,
+                   disp_postp=disp_postp, head=b['head'])
+        if self.lr_check:
+            out['disp_mask'] = b['disp_mask']
+        return out
 
     @staticmethod
     def pack_detections(out, scaled=False, n_real=None):
@@ -367,7 +379,7 @@ class InflightPipelines:
 
     def __getattr__(self, name):   # geometry / thresholds of the (identical) contexts: batch, max_det, stereo, ...
         if name in ('batch', 'max_det', 'stereo', 'height', 'width', 'ori_h', 'ori_w', 'agg_layers', 'agg3d_layers', 'split_bf16',
-                    'rgb_only', 'full_res', 'sgbm', 'takes_right', 'depth_method'):
+                    'rgb_only', 'full_res', 'sgbm', 'takes_right', 'depth_method', 'lr_check', 'lr_max_diff'):
             return getattr(self.pipes[0], name)
         raise AttributeError(name)
 

@@ -29,6 +29,13 @@ aggregation and soft-argmin" with D = max_disp levels at IMAGE resolution (192 x
              first layer run as ONE kernel (st_costvolume_agg3d: the volume between them never reaches memory; same bits)
   disparity  disp = sum_d d * softmax_d(temperature * cost) in pixels, no upsampling step (st_softargmin), 0 outside the
              original image, three identical channels (st_disp_upsample_pack with scale 1)
+LEFT-RIGHT CHECK (`lr_check=True`, off by default; DESIGN.md "Left-right check of the stereo module"): the final volume is
+read a second time along its diagonals as the RIGHT view's volume (VR[x'][d] = V[x'+d][d], 0 past the image), its soft-argmin
+d_R is compared with d_L at the matched column, and pixels whose match lies outside the right image or whose two disparities
+differ by more than `lr_max_diff` image pixels become 0 in `disp_postp` (and in `disp_mask`): what "0 = invalid" means to
+extract_depth (ocsort_disparity.py:136-175) and to StereoSGBM's left-right check.  Valid pixels keep their bits
+(st_softargmin_right + st_lr_check_pack, csrc/lr_check.hip).
+
 A raw-pixel correlation at full resolution was withdrawn in round 3 (not a matcher); this mode correlates learned stage-1
 FEATURES brought to image resolution.  It runs at ~0.53 of the default module's rate (bench.py --fullres-leg) and exists so
 that the literal sizing is a tested, benched product path, not only a kernel measurement.
@@ -50,8 +57,16 @@ class StereoCostVolume(nn.Module):
     `agg.{l}.weight` / `agg.{l}.bias`, so under the MOT shell a checkpoint carries `stereo.agg.{l}.*`."""
 
     def __init__(self, max_disp=192, feat_stride=4, temperature=32.0, agg_layers=0, agg3d_layers=0, full_res=False,
-                 full_res_channels=8, feat_channels=64):
+                 full_res_channels=8, feat_channels=64, lr_check=False, lr_max_diff=1.0):
         super().__init__()
+        import math
+        try:
+            lr_ok = math.isfinite(float(lr_max_diff)) and float(lr_max_diff) >= 0.0
+        except (TypeError, ValueError):
+            lr_ok = False
+        if not lr_ok:
+            raise ValueError(f'lr_max_diff must be a finite number of image pixels >= 0 (got {lr_max_diff!r})')
+        self.lr_check, self.lr_max_diff = bool(lr_check), float(lr_max_diff)
         if feat_stride != 4:
             raise NotImplementedError('only feat_stride=4 (stage1 features) is wired up')
         if max_disp % feat_stride:
@@ -110,6 +125,7 @@ class StereoCostVolume(nn.Module):
         self._fr_fused = False
         self._taps3d = None    # (weights version, [(27 host floats as a ctypes array, bias)])
         self._vol = None
+        self._lr = None        # left-right check scratch per (device, stream): right disparity (+ the volume where no layer keeps one)
         self.variant = -1      # conv tile variant of the aggregation layers (-1 = library default, or autotune())
         self.timing = False    # record events around every aggregation conv (bench.py roofline accounting)
         self._events = []
@@ -185,6 +201,27 @@ class StereoCostVolume(nn.Module):
                                 torch.zeros(N, Hf, Wf, D, dtype=torch.float32, device=dev))
         return v
 
+    def _lr_scratch(self, dev, N, Hl, Wl, volume=False):
+        """Left-right check: the right view's disparity (N,Hl,Wl) and, for a module without aggregation layers (which
+        otherwise never writes its volume), the volume itself.  Owned per (device, stream) like every scratch buffer."""
+        if self._lr is None:
+            self._lr = {}
+        k = self._scratch_key(dev)
+        b = self._lr.get(k)
+        if b is None or b['dr'].shape != (N, Hl, Wl):
+            b = self._lr[k] = dict(dr=torch.empty(N, Hl, Wl, dtype=torch.float32, device=dev), vol=None)
+        if volume and b['vol'] is None:
+            b['vol'] = torch.empty(N, Hl, Wl, self.levels, dtype=torch.float32, device=dev)
+        return b
+
+    def _lr_pack(self, vol, disp, N, Hl, Wl, scale, H, W, valid_hw, disp_postp, disp_mask, stream, dev):
+        """Rules 2-5 of the left-right check on the final volume `vol` and its left disparity `disp`."""
+        dr = self._lr_scratch(dev, N, Hl, Wl)['dr']
+        check(self.lib.st_softargmin_right(ptr(vol), N, Hl, Wl, self.levels, self.temperature, ptr(dr), stream),
+              'st_softargmin_right')
+        check(self.lib.st_lr_check_pack(ptr(disp), ptr(dr), N, Hl, Wl, scale, H, W, int(valid_hw[0]), int(valid_hw[1]),
+                                        self.lr_max_diff, ptr(disp_postp), ptr(disp_mask), stream), 'st_lr_check_pack')
+
     def autotune(self, dev, N, Hf, Wf, reps=5, candidates=tuple(range(22)) + (42, 43)):
         """Pick the aggregation convs' tile variant by measurement (same policy as st_detector_autotune:
         min over `reps` individually timed launches).  Returns the chosen variant id."""
@@ -233,12 +270,15 @@ class StereoCostVolume(nn.Module):
         return t
 
     # ---- compute ------------------------------------------------------------------------------------------
-    def compute(self, engine, img, right, valid_hw, disp_lr=None, disp_postp=None, cost_out=None):
+    def compute(self, engine, img, right, valid_hw, disp_lr=None, disp_postp=None, cost_out=None, disp_mask=None):
         """engine: a HipDetector built with stereo=True.  img/right: (N,3,H,W) fp32 CUDA, or two RawChunk (uint8 frames).
         Runs phase 0 (features of left+right) then cost volume (+ aggregation) + soft-argmin + upsample.
-        Returns disp_postp (N,3,H,W); phase-0 activations stay in the engine workspace for phase 1."""
+        Returns disp_postp (N,3,H,W); phase-0 activations stay in the engine workspace for phase 1.
+        disp_mask: optional (N,1,H,W) fp32 buffer, with lr_check=True only: 1 = valid, 0 = failed the left-right check or padding."""
         if not engine.stereo:
             raise ValueError('StereoCostVolume needs a detector context built with stereo=True')
+        if disp_mask is not None and not self.lr_check:
+            raise ValueError('disp_mask is written by the left-right check: build the module with lr_check=True')
         N, H, W = engine.batch, engine.height, engine.width
         s = self.feat_stride
         dev = img.device
@@ -257,11 +297,15 @@ class StereoCostVolume(nn.Module):
             disp_postp = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
         stream = current_stream()
         if self.full_res:
-            return self._compute_full_res(feat, N, Hf, Wf, Cf, ld, valid_hw, disp_postp, cost_out, stream, dev, H, W)
+            return self._compute_full_res(feat, N, Hf, Wf, Cf, ld, valid_hw, disp_postp, cost_out, stream, dev, H, W,
+                                          disp_mask)
         if self.timing:
             cv0, cv1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             cv0.record()
         if self.agg_layers == 0 and self.agg3d_layers == 0:
+            if self.lr_check and cost_out is None:     # the check reads the volume: materialise it beside the disparity
+                cost_out = self._lr_scratch(dev, N, Hf, Wf, volume=True)['vol']
+            va = cost_out
             check(self.lib.st_costvolume_softargmin(C.c_void_p(fl), C.c_void_p(fr), N, Hf, Wf, Cf, ld, D,
                                                     self.temperature, ptr(cost_out), ptr(disp_lr), stream),
                   'st_costvolume_softargmin')
@@ -296,6 +340,9 @@ class StereoCostVolume(nn.Module):
                 cost_out.copy_(va)
             check(self.lib.st_softargmin(ptr(va), N, Hf, Wf, D, self.temperature, ptr(disp_lr), stream),
                   'st_softargmin')
+        if self.lr_check:
+            self._lr_pack(va, disp_lr, N, Hf, Wf, s, H, W, valid_hw, disp_postp, disp_mask, stream, dev)
+            return disp_postp
         check(self.lib.st_disp_upsample_pack(ptr(disp_lr), N, Hf, Wf, s, H, W, int(valid_hw[0]), int(valid_hw[1]),
                                              ptr(disp_postp), stream), 'st_disp_upsample_pack')
         return disp_postp
@@ -340,13 +387,14 @@ class StereoCostVolume(nn.Module):
             fr['vb'] = torch.empty(N, H, W, D, dtype=torch.float32, device=dev)
         return fr
 
-    def _compute_full_res(self, feat, N, Hf, Wf, Cf, ld, valid_hw, disp_postp, cost_out, stream, dev, H, W):
+    def _compute_full_res(self, feat, N, Hf, Wf, Cf, ld, valid_hw, disp_postp, cost_out, stream, dev, H, W, disp_mask=None):
         if Cf != self.reduce.in_channels:
             raise ValueError(f'full_res: the detector\'s stage-1 features have {Cf} channels, the module was built for '
                              f'feat_channels={self.reduce.in_channels}')
         s, D, Cr = self.feat_stride, self.levels, self.reduce.out_channels
+        # (the left-right check reads the aggregated volume: it takes the forms that write it, same bits by construction)
         single_kernel = (self.agg3d_layers == 1 and cost_out is None and self.fuse_first_layer and self.fuse_softargmin and
-                         D in (48, 96, 192) and self.lib.st_costvolume_agg3d_supported(Cr, D) == 1)
+                         not self.lr_check and D in (48, 96, 192) and self.lib.st_costvolume_agg3d_supported(Cr, D) == 1)
         b = self.full_res_buffers(dev, N, Hf, Wf, need_volume=not single_kernel)
         wp, bp = self._pack_reduce(dev)
         ev = []
@@ -408,8 +456,11 @@ class StereoCostVolume(nn.Module):
         if cost_out is not None:
             cost_out.copy_(va)
         check(self.lib.st_softargmin(ptr(va), N, H, W, D, self.temperature, ptr(b['disp']), stream), 'st_softargmin')
-        check(self.lib.st_disp_upsample_pack(ptr(b['disp']), N, H, W, 1, H, W, int(valid_hw[0]), int(valid_hw[1]),
-                                             ptr(disp_postp), stream), 'st_disp_upsample_pack')
+        if self.lr_check:
+            self._lr_pack(va, b['disp'], N, H, W, 1, H, W, valid_hw, disp_postp, disp_mask, stream, dev)
+        else:
+            check(self.lib.st_disp_upsample_pack(ptr(b['disp']), N, H, W, 1, H, W, int(valid_hw[0]), int(valid_hw[1]),
+                                                 ptr(disp_postp), stream), 'st_disp_upsample_pack')
         mark()
         if self.timing:
             self._fr_events = ev
