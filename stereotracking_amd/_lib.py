@@ -53,6 +53,17 @@ class StTrackerConfig(C.Structure):
     ]
 
 
+TRACKER_OPTIONS = tuple(name for name, _ in StTrackerConfig._fields_[1:])
+
+
+def tracker_config(obj_score_thr, init_track_thr, weight_iou_with_det_scores, match_iou_thr, num_tentatives,
+                   vel_consist_weight, vel_delta_t, num_frames_retain):
+    """StTrackerConfig of the tracker options, under their names in OCSORTTracker_Disparity's constructor."""
+    return StTrackerConfig(C.sizeof(StTrackerConfig), float(obj_score_thr), float(init_track_thr),
+                           int(bool(weight_iou_with_det_scores)), float(match_iou_thr), int(num_tentatives),
+                           float(vel_consist_weight), int(vel_delta_t), int(num_frames_retain))
+
+
 class StCmcParams(C.Structure):
     _fields_ = [('struct_size', C.c_int), ('step', C.c_int), ('winsize', C.c_int), ('ransac_thr', C.c_float),
                 ('min_inlier_ratio', C.c_float)]

@@ -12,7 +12,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import StTrackerConfig, check, current_stream, ptr
+from ._lib import check, current_stream, ptr
+from .records import REC_FLOATS, TRACK_ROW
 
 
 class BatchedGpuTracker:
@@ -29,9 +30,8 @@ class BatchedGpuTracker:
         self.lib = _lib.load()
         self.batch, self.max_tracks, self.max_dets = int(batch), int(max_tracks), int(max_dets)
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        cfg = StTrackerConfig(C.sizeof(StTrackerConfig), float(obj_score_thr), float(init_track_thr),
-                              int(bool(weight_iou_with_det_scores)), float(match_iou_thr), int(num_tentatives),
-                              float(vel_consist_weight), int(vel_delta_t), int(num_frames_retain))
+        cfg = _lib.tracker_config(obj_score_thr, init_track_thr, weight_iou_with_det_scores, match_iou_thr,
+                                  num_tentatives, vel_consist_weight, vel_delta_t, num_frames_retain)
         h = C.c_void_p()
         check(self.lib.st_batched_tracker_create(C.byref(cfg), self.batch, self.max_tracks, self.max_dets, C.byref(h)),
               'st_batched_tracker_create')
@@ -39,7 +39,7 @@ class BatchedGpuTracker:
         self.state = torch.zeros(self.lib.st_batched_tracker_state_bytes(h), dtype=torch.uint8, device=self.device)
         self.scratch = torch.empty(self.lib.st_batched_tracker_scratch_bytes(h), dtype=torch.uint8, device=self.device)
         B, M = self.batch, self.max_dets
-        self.rows = torch.zeros(B, M, 8, dtype=torch.float32, device=self.device)
+        self.rows = torch.zeros(B, M, TRACK_ROW.floats, dtype=torch.float32, device=self.device)
         self.ids = torch.zeros(B, M, dtype=torch.int64, device=self.device)
         self.n = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
@@ -60,7 +60,7 @@ class BatchedGpuTracker:
         """frame_ids (batch,) int32, dets (batch, max_dets, 8) float32, counts (batch,) int32 - CUDA tensors.
         check_status: one host sync to raise on a capacity overflow (False: read `self.status` yourself).  A non-zero
         status is sticky per sequence: the device state of that sequence is invalid until a step with frame_id 0."""
-        for t, dt, shape in ((frame_ids, torch.int32, (self.batch,)), (dets, torch.float32, (self.batch, self.max_dets, 8)),
+        for t, dt, shape in ((frame_ids, torch.int32, (self.batch,)), (dets, torch.float32, (self.batch, self.max_dets, REC_FLOATS)),
                              (counts, torch.int32, (self.batch,))):
             if not (t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
                 raise ValueError(f'expected a contiguous CUDA {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}')

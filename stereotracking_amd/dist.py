@@ -12,6 +12,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import records as _records
+
 
 def world():
     if dist.is_available() and dist.is_initialized():
@@ -117,14 +119,15 @@ class DetectionOverflow(RuntimeError):
 def unpack_frame(record, frame=None):
     """One frame record (M + 1, 8) (StereoDensePipeline.pack_detections) -> dict of tensors for the tracker.
     Raises DetectionOverflow when the frame kept more boxes than the buffer has rows."""
-    k, cap = int(record[0, 0]), int(record[0, 1])
+    k, cap = int(record[_records.REC_HEADER, _records.REC_COUNT]), int(record[_records.REC_HEADER, _records.REC_CAP])
     if k > cap:
         raise DetectionOverflow(f'frame {frame}: {k} detections kept but the detection buffer has {cap} rows; '
                                 f'build the pipeline with a larger max_det')
-    b = record[1:1 + k]
-    return dict(bboxes=b[:, :4], scores=b[:, 4], labels=b[:, 5].long(), depth=b[:, 6], scales=b[:, 7])
+    b, R = record[1:1 + k], _records
+    return dict(bboxes=b[:, R.BOX], scores=b[:, R.SCORE], labels=b[:, R.LABEL].long(), depth=b[:, R.REC_DEPTH],
+                scales=b[:, R.REC_SCALE])
 
 
 def record_counts(records):
     """(F, M + 1, 8) records -> (counts (F,) int64, capacity M)."""
-    return records[:, 0, 0].long(), records.shape[1] - 1
+    return records[:, _records.REC_HEADER, _records.REC_COUNT].long(), records.shape[1] - 1

@@ -13,7 +13,7 @@ Per-box depth: OCSORT_Disparity(depth_extraction=...) picks the estimator of eve
 reference's default extract_depth) or one of its depth-extraction comparison, 'truncated_mean', 'mean', 'median' or
 'center' (DESIGN.md §11).
 """
-import ctypes as C
+import time
 
 import numpy as np
 import torch
@@ -22,7 +22,10 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, current_stream, ptr
+from . import records, shell_inputs
+from .pipeline import InflightPipelines, depth_method_code, launch_box_depth
 from .registry import MODELS, TASK_UTILS
+from .shell_inputs import RawFrames
 from .structures import InstanceData, TrackDataSample
 from .trackers import OCSORTTracker_Disparity  # noqa: F401  (registers the tracker)
 from .motion import KalmanFilter  # noqa: F401  (registers the motion model)
@@ -141,58 +144,6 @@ class TrackDataPreprocessor_Disparity_V1(nn.Module):
         return dict(inputs=out, data_samples=samples)
 
 
-class RawFrames:
-    """N equal-sized uint8 CUDA frames (1,3,h,w) of one input key, NOT yet converted: what test_step hands to
-    predict() for frames uploaded raw.  predict() converts a chunk at a time (torch.cat of the chunk's frames +
-    st_pack_raw_inputs: cast + pad in one HIP pass) inside the pipelined submit, so the conversion
-    of chunk i+3 overlaps the dense work of chunks i..i+2 and no (N,1,3,H,W) fp32 copy of the whole call exists.
-    Values are exactly those of TrackDataPreprocessor_Disparity_V1.forward (reference
-    data_preprocessor_disparity_v1.py:21-84 + utils/misc.py:13-64)."""
-
-    def __init__(self, frames, pad_hw, pad_value):
-        self.frames, self.pad_hw, self.pad_value = frames, (int(pad_hw[0]), int(pad_hw[1])), float(pad_value)
-        self.hw = tuple(frames[0].shape[-2:])
-        self.device = frames[0].device
-
-    def __len__(self):
-        return len(self.frames)
-
-    def chunk(self, s, e, B):
-        """frames [s, e) (+ the last one repeated up to B) -> (B,3,H,W) fp32, padded with pad_value."""
-        fr = self.frames[s:e]
-        fr = fr + [fr[-1]] * (B - len(fr))
-        (h, w), (H, W) = self.hw, self.pad_hw
-        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
-        lib = _lib.load()
-        if (B <= 32 and w % 4 == 0 and W % 4 == 0 and
-                all(f.is_contiguous() and f.dtype == torch.uint8 and f.data_ptr() % 4 == 0 for f in fr)):
-            # the frames stay where the dataloader put them: their pointers travel in the kernel arguments
-            # (no torch.cat staging copy: 73 us per input and chunk at 8 x 720 x 1280)
-            ptrs = (C.c_void_p * B)(*[f.data_ptr() for f in fr])
-            check(lib.st_pack_raw_frames(ptrs, B, h, w, H, W, self.pad_value, ptr(out), current_stream()),
-                  'st_pack_raw_frames')
-            return out
-        raw = torch.cat(fr, dim=0)
-        check(lib.st_pack_raw_inputs(ptr(raw), None, B, h, w, H, W, self.pad_value, ptr(out), None, None,
-                                     current_stream()), 'st_pack_raw_inputs')
-        return out
-
-    def raw_chunk(self, s, e, B, runner):
-        """frames [s, e) (+ the last one repeated up to B) as an engine.RawChunk - the stem kernel casts + pads them while it
-        stages its input windows (st_detector_forward_phase0_raw), no fp32 image exists - or None when the frames do
-        not qualify (width % 4, alignment, non-integral pad value, padded size of another plan)."""
-        from .engine import RawChunk
-        fr = self.frames[s:e]
-        fr = fr + [fr[-1]] * (B - len(fr))
-        if self.pad_hw != (runner.height, runner.width) or not RawChunk.supported(fr, self.pad_value):
-            return None
-        return RawChunk(fr, self.pad_value)
-
-    def dense(self):
-        """The (N,1,3,H,W) fp32 tensor the preprocessor would have produced (for callers that want it)."""
-        return self.chunk(0, len(self.frames), len(self.frames))[:, None]
-
-
 def pack_raw_inputs(img_u8=None, disp_u16=None, pad_size_divisor=32, img_pad=114.0):
     """Device-side input pipeline for frames uploaded raw: uint8 (N,3,h,w) image and/or
     uint16 (N,h,w) disparity PNG codes, both CUDA tensors -> dict(img, disp_postp, disp_mask) fp32 padded to
@@ -305,7 +256,6 @@ class OCSORT_Disparity(nn.Module):
                  results_device='cpu', autotune=True, tuning_cache=None, results_csv=None, split_bf16=None,
                  queue_depth=1, depth_extraction='reference'):
         super().__init__()
-        from .pipeline import depth_method_code
         depth_method_code(depth_extraction)     # ValueError for an unknown estimator, before anything is built
         self.depth_extraction = depth_extraction
         self.data_preprocessor = MODELS.build(data_preprocessor) if data_preprocessor is not None else None
@@ -357,12 +307,8 @@ class OCSORT_Disparity(nn.Module):
             self.detector.init_weights()
 
     def test_step(self, data):
-        import time
         t0 = time.perf_counter()
-        if self._pre_lazy:     # decided once from the preprocessor's signature (__init__), not by catching TypeError
-            data = self.data_preprocessor(data, False, lazy_raw=True)
-        else:                  # a preprocessor without the lazy option (e.g. mmengine's own class)
-            data = self.data_preprocessor(data, False)
+        data = shell_inputs.preprocess(self, data)
         self.timings['pre_s'] += time.perf_counter() - t0
         return self.forward(data['inputs'], data['data_samples'], mode='predict')
 
@@ -380,7 +326,6 @@ class OCSORT_Disparity(nn.Module):
     def dense_runner(self, ori_hw, stereo, batch=None):
         """InflightPipelines context set for (batch, ori_hw, stereo), built from this model's config and
         loaded from its state_dict (reference keys `detector.*`, plus `stereo.agg.*` of the new module)."""
-        from .pipeline import InflightPipelines
         det = self.detector
         cfg = det.test_cfg
         nms = cfg.get('nms', dict(type='nms', iou_threshold=0.65))
@@ -460,27 +405,20 @@ class OCSORT_Disparity(nn.Module):
         """ONE st_box_depth launch for a whole batch: disp (N,C,H,W), boxes (N,M,4), counts (N,) int32 or None
         (= all M rows) -> depth (N,M), scales (N,M), scaled boxes (N,M,4).  The estimator is `depth_extraction`
         (st_box_depth_method for the alternatives)."""
-        from .pipeline import depth_method_code
-        method = depth_method_code(self.depth_extraction)
         N, M = boxes.shape[0], boxes.shape[1]
         dev = boxes.device
         if M == 0:
             return torch.zeros(N, 0, device=dev), torch.zeros(N, 0, device=dev), torch.zeros(N, 0, 4, device=dev)
-        depth = torch.empty(N, M, device=dev)      # st_box_depth defines every row (0 past the count)
-        scales = torch.empty(N, M, device=dev)
-        sboxes = torch.empty(N, M, 4, device=dev)
+        out = (torch.empty(N, M, device=dev), torch.empty(N, M, device=dev),      # depth, scales, scaled boxes:
+               torch.empty(N, M, 4, device=dev))                                   # st_box_depth defines every row
         _, Cc, H, W = disp.shape
         disp = disp.float().contiguous()
         if counts is None:
             counts = torch.full((N,), M, dtype=torch.int32, device=dev)
         boxes = boxes.float().contiguous()
-        args = (ptr(disp), Cc * H * W, N, H, W, ptr(boxes), ptr(counts), M, float(baseline),
-                float(focal), None, 0, current_stream(), ptr(depth), ptr(scales), ptr(sboxes))
-        if method == 0:
-            check(self.lib.st_box_depth(*args), 'st_box_depth')
-        else:
-            check(self.lib.st_box_depth_method(*args, method), 'st_box_depth_method')
-        return depth, scales, sboxes
+        launch_box_depth(self.lib, disp, boxes, counts, baseline, focal, depth_method_code(self.depth_extraction), out,
+                         Cc * H * W)
+        return out
 
     # ---- predict (ocsort_disparity.py:50-111) ------------------------------------------------------------
     def predict(self, inputs, data_samples, **kwargs):
@@ -494,14 +432,10 @@ class OCSORT_Disparity(nn.Module):
         submitted while call k drains, so the device never idles between calls (fill + drain cost 5 % at 64 frames per
         call).  Stands where mmengine's TestLoop calls `model.test_step(data_batch)` per batch
         (reference mot/base.py:68-113 is the per-call entry this keeps)."""
-        import time
         prev = None
         for data in data_iter:
             t0 = time.perf_counter()
-            if self._pre_lazy:
-                data = self.data_preprocessor(data, False, lazy_raw=True)
-            else:
-                data = self.data_preprocessor(data, False)
+            data = shell_inputs.preprocess(self, data)
             self.timings['pre_s'] += time.perf_counter() - t0
             st = self.begin(data['inputs'], data['data_samples'])
             if prev is not None:
@@ -513,76 +447,22 @@ class OCSORT_Disparity(nn.Module):
     def begin(self, inputs, data_samples, **kwargs):
         """Validate one call's inputs and plan its chunks; nothing is launched yet (finish() does, or the finish() of
         the call before this one when it is passed there as `lookahead`)."""
-        img, disp_postp = inputs['img'], inputs.get('disp_postp')
-        depth_postp = inputs.get('depth_postp', None)
-
-        def unwrap(t, name):      # (N,1,C,H,W) tensor -> (N,C,H,W); RawFrames stay lazy (converted per chunk)
-            if t is None or isinstance(t, RawFrames):
-                return t
-            assert t.dim() == 5, f'The {name} must be 5D Tensor (N, T, C, H, W).'
-            assert t.size(1) == 1, 'one key frame per sample (T = 1)'
-            return t[:, 0]
-        img = unwrap(img, 'img')
+        img, second, gt, stereo, ori = shell_inputs.plan_inputs(self, inputs, data_samples, 'OCSORT_Disparity')
         N = len(img)
-        assert len(data_samples) == N
-        if not (img.device.type == 'cuda'):
-            raise RuntimeError('OCSORT_Disparity runs on the HIP path only: inputs must be CUDA tensors')
-        stereo = disp_postp is None
-        if stereo:
-            if self.stereo is None or inputs.get('right') is None:
-                raise KeyError("inputs need 'disp_postp', or 'right' with a stereo module configured")
-            second = unwrap(inputs['right'], 'right')
-        else:
-            second = unwrap(disp_postp, 'disp_postp')
-            if isinstance(second, RawFrames):
-                second = second.dense()[:, 0]      # a uint8 disparity is unusual: convert it eagerly
-        gt = unwrap(depth_postp, 'depth_postp')
-        if isinstance(gt, RawFrames):
-            gt = gt.dense()[:, 0]
-        metas = [s.metainfo for s in data_samples]
-        pad_hw = img.pad_hw if isinstance(img, RawFrames) else tuple(img.shape[-2:])
-        ori = tuple(int(v) for v in metas[0].get('ori_shape', pad_hw)[:2])
-        for m in metas[1:]:
-            if tuple(int(v) for v in m.get('ori_shape', ori)[:2]) != ori:
-                raise NotImplementedError('one batched launch plan needs a uniform ori_shape')
-        if stereo and isinstance(self.stereo, _sgbm.StereoSGBM):
-            for m in metas:
-                if 'img_shape' in m and tuple(int(v) for v in m['img_shape'][:2]) != ori:
-                    raise NotImplementedError(
-                        f"StereoSGBM matches at the original resolution: img_shape {tuple(m['img_shape'][:2])} differs "
-                        f"from ori_shape {ori} (the reference matched before resizing; that order is not restated)")
         B = min(self.dense_batch, N)      # a call with fewer frames than dense_batch gets a plan of its own size
         runner = self.dense_runner(ori, stereo, B)
         return dict(img=img, second=second, gt=gt, stereo=stereo, N=N, B=B, runner=runner, dev=img.device,
                     data_samples=data_samples, kwargs=kwargs, jobs={}, submitted=0,
                     chunks=[(s, min(s + B, N)) for s in range(0, N, B)])
 
-    @staticmethod
-    def _padded(t, s, e, B):
-        if isinstance(t, RawFrames):
-            return t.chunk(s, e, B)
-        t = t[s:e].float().contiguous()
-        if e - s < B:      # last chunk: repeat its last frame (results of the padding are ignored)
-            t = torch.cat([t, t[-1:].expand(B - (e - s), *t.shape[1:])])
-        return t
-
     def _submit_next(self, st):
         """Enqueue call `st`'s next chunk on the runner's next context (round-robin)."""
-        import time
         ts = time.perf_counter()
         runner, B, stereo = st['runner'], st['B'], st['stereo']
         ci = st['submitted']
         st['submitted'] += 1
         s, e = st['chunks'][ci]
-        a = b = None
-        if self.raw_stem and isinstance(st['img'], RawFrames):
-            if stereo and isinstance(st['second'], RawFrames):
-                a, b = st['img'].raw_chunk(s, e, B, runner), st['second'].raw_chunk(s, e, B, runner)
-            elif not stereo:      # disparity-input configuration: the image raw, the fp32 disparity as it is
-                a = st['img'].raw_chunk(s, e, B, runner)
-                b = self._padded(st['second'], s, e, B) if a is not None else None
-        if a is None or b is None:      # fp32 tensors (or frames the stem cannot read raw): cast + pad as a pass of its own
-            a, b = self._padded(st['img'], s, e, B), self._padded(st['second'], s, e, B)
+        a, b = shell_inputs.chunk_inputs(self, st['img'], st['second'], stereo, s, e, B, runner)
         holder = {}
         # staging buffers of a context alternate: it is resubmitted before the chunk it just finished is consumed
         turns = self._staging.setdefault(('ctx_turns', id(runner)), [0] * len(runner))
@@ -672,16 +552,12 @@ class OCSORT_Disparity(nn.Module):
     def finish(self, st, lookahead=None):
         """Run call `st` to completion and return its samples.  `lookahead`: the begin() state of the NEXT call on the
         same runner - as this call's contexts free up they are refilled with that call's first chunks."""
-        import time
         from .dist import DetectionOverflow
         runner, B, N, dev, gt = st['runner'], st['B'], st['N'], st['dev'], st['gt']
         data_samples, kwargs, chunks, jobs = st['data_samples'], st['kwargs'], st['chunks'], st['jobs']
         if lookahead is not None and (lookahead['runner'] is not runner or lookahead is st):
             lookahead = None
         t_host0 = time.perf_counter()
-
-        def padded(t, s, e):
-            return self._padded(t, s, e, B)
 
         def refill():       # one context is free: this call's next chunk, else the next call's
             if st['submitted'] < len(chunks):
@@ -732,41 +608,33 @@ class OCSORT_Disparity(nn.Module):
                     trows, tids, tcnt = self._cmc_track_records(fids, chunk_np, job['cmc'])
                 else:
                     trows, tids, tcnt = self.tracker.track_records(fids, chunk_np)
-                det_labels = torch.from_numpy(chunk_np[:, 1:, 5].astype(np.int64))
-                det_prior = torch.from_numpy(chunk_np[:, 1:, 12].astype(np.int64))
-                trk_labels = torch.from_numpy(trows[:, :, 5].astype(np.int64))
-                counts_h = chunk_np[:, 0, 0].astype(np.int64).tolist()
+                det_labels = records.int_column(chunk_np[:, 1:], records.LABEL)
+                det_prior = records.int_column(chunk_np[:, 1:], records.REC_PRIOR)
+                trk_labels = records.int_column(trows, records.LABEL)
+                counts_h = chunk_np[:, records.REC_HEADER, records.REC_COUNT].astype(np.int64).tolist()
                 chunk, trows, tids = torch.from_numpy(chunk_np), torch.from_numpy(trows), torch.from_numpy(tids)
-                for i, n in enumerate(range(s, e)):
+                for i, sample in enumerate(data_samples[s:e]):
                     k, m = counts_h[i], int(tcnt[i])
-                    rows, tr = chunk[i, 1:1 + k], trows[i, :m]
-                    data_samples[n].pred_det_instances = InstanceData(bboxes=rows[:, 0:4], scores=rows[:, 4],
-                                                                      labels=det_labels[i, :k],
-                                                                      prior_idx=det_prior[i, :k])   # (:107-108)
-                    tracks = InstanceData()
-                    tracks['bboxes'] = tr[:, 0:4]                     # already unscaled (:95-97)
-                    tracks['labels'] = trk_labels[i, :m]
-                    tracks['scores'] = tr[:, 4]
-                    tracks['scales'] = tr[:, 7]
-                    tracks['depth'] = tr[:, 6]
-                    tracks.instances_id = tids[i, :m]
-                    tracks_of.append(tracks)
+                    sample.pred_det_instances = records.detections(chunk[i, 1:1 + k], det_labels[i, :k], det_prior[i, :k])
+                    # (:107-108); the track rows are already unscaled (:95-97)
+                    tracks_of.append(records.tracks(trows[i, :m], trk_labels[i, :m], tids[i, :m], records.TRACK_ROW))
             else:
               cj = job['cmc']
               if cj is not None:
                   cj['ev'].synchronize()
               for n in range(s, e):
                 r = rec[n - s]
-                k, cap = int(r[0, 0]), int(r[0, 1])
+                k, cap = int(r[records.REC_HEADER, records.REC_COUNT]), int(r[records.REC_HEADER, records.REC_CAP])
                 if k > cap:
                     raise DetectionOverflow(f'frame {n}: {k} detections kept but the detection buffer has {cap} rows; '
                                             f'build the model with a larger max_det')
                 rows = r[1:1 + k].clone()      # the staging buffer is reused by a later chunk
-                labels = rows[:, 5].long()
                 sample = data_samples[n]
                 # reference :82-86: the tracker consumes the depth-SCALED boxes + scales + depth
-                sample.pred_det_instances = InstanceData(bboxes=rows[:, 8:12], scores=rows[:, 4], labels=labels,
-                                                         scales=rows[:, 7], depth=rows[:, 6])
+                labels = rows[:, records.LABEL].long()
+                sample.pred_det_instances = InstanceData(bboxes=rows[:, records.REC_SCALED_BOX], scores=rows[:, records.SCORE],
+                                                         labels=labels, scales=rows[:, records.REC_SCALE],
+                                                         depth=rows[:, records.REC_DEPTH])
                 cimg = None
                 if cj is not None:
                     from .cmc import CmcFrame
@@ -774,8 +642,8 @@ class OCSORT_Disparity(nn.Module):
                     cimg = CmcFrame(cj['planes'][i + 1:i + 2], cj['fids'][i], cj['host'][i].numpy(), cj['warp_src'][i])
                 tracks = self.tracker.track(model=self, img=cimg, feats=None, data_sample=sample, **kwargs)
                 tracks['bboxes'] = scale_bbox(tracks.bboxes, 1 / tracks.scales)      # unscale (:95-97)
-                sample.pred_det_instances = InstanceData(bboxes=rows[:, 0:4].clone(), scores=rows[:, 4].clone(),
-                                                         labels=labels, prior_idx=rows[:, 12].long())   # (:107-108)
+                sample.pred_det_instances = InstanceData(bboxes=rows[:, records.BOX].clone(), scores=rows[:, records.SCORE].clone(),
+                                                         labels=labels, prior_idx=rows[:, records.REC_PRIOR].long())   # (:107-108)
                 tracks_of.append(tracks)
             self.timings['tracker_s'] += time.perf_counter() - t0
             # reference :99-104: depth (and gt depth) of the UNSCALED track boxes - ONE batched launch per chunk, on a
@@ -801,7 +669,7 @@ class OCSORT_Disparity(nn.Module):
                 d = self._box_depth(job['disp'], tbd, tcd, self.baseline, self.focal_length)[0]
                 cols = [d]
                 if gt is not None:
-                    cols.append(self._box_depth(padded(gt, s, e), tbd, tcd, -1.0, 1.0)[0])
+                    cols.append(self._box_depth(shell_inputs.padded(gt, s, e, B), tbd, tcd, -1.0, 1.0)[0])
                 dh = self._pinned(('track_depth', id(runner), ci), (len(cols), B, mt))   # read at the end of the call
                 dh.copy_(torch.stack(cols), non_blocking=True)
                 ev2 = torch.cuda.Event()

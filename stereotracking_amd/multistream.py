@@ -21,16 +21,12 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import StStreamTick, StTrackerConfig, check, current_stream, ptr
+from . import _lib, records, shell_inputs
+from ._lib import StStreamTick, check, current_stream, ptr
 from .batched_assoc import BatchedGpuTracker
 from .registry import MODELS
-from .structures import InstanceData
 
 MAX_STREAMS = 128        # ST_STREAM_MAX_STREAMS: the tick's routing travels in the kernel arguments
-_HDR, _ROW, _DET = 4, 10, 8   # ST_STREAM_HDR_INTS / ST_STREAM_ROW_FLOATS / ST_STREAM_DET_FLOATS
-_TRACKER_OPTIONS = ('obj_score_thr', 'init_track_thr', 'weight_iou_with_det_scores', 'match_iou_thr', 'num_tentatives',
-                    'vel_consist_weight', 'vel_delta_t', 'num_frames_retain')
 
 
 class StreamOverflow(RuntimeError):
@@ -74,7 +70,7 @@ class MultiStreamTracker:
             raise ValueError(f'max_dets must be in [1, max_det = {model.max_det}] of the wrapped model, got {max_dets}')
         if self.max_tracks < 1:
             raise ValueError(f'max_tracks must be positive, got {max_tracks}')
-        self.tracker_options = {k: getattr(trk, k) for k in _TRACKER_OPTIONS}
+        self.tracker_options = {k: getattr(trk, k) for k in _lib.TRACKER_OPTIONS}
         self._check_tracker_options()
         self.chunk = max(1, min(int(model.dense_batch), self.streams))     # frames per dense launch plan
         self.max_chunks = -(-self.streams // self.chunk)
@@ -86,11 +82,7 @@ class MultiStreamTracker:
 
     def _check_tracker_options(self):
         """The options the batched association refuses, refused here - on the host, before a device is touched."""
-        o = self.tracker_options
-        cfg = StTrackerConfig(C.sizeof(StTrackerConfig), float(o['obj_score_thr']), float(o['init_track_thr']),
-                              int(bool(o['weight_iou_with_det_scores'])), float(o['match_iou_thr']),
-                              int(o['num_tentatives']), float(o['vel_consist_weight']), int(o['vel_delta_t']),
-                              int(o['num_frames_retain']))
+        cfg = _lib.tracker_config(**self.tracker_options)
         lib, h = _lib.load(), C.c_void_p()
         try:
             check(lib.st_batched_tracker_create(C.byref(cfg), self.streams, self.max_tracks, self.max_dets, C.byref(h)),
@@ -107,9 +99,8 @@ class MultiStreamTracker:
             raise ValueError('empty tick: a tick carries at least one frame')
         if len(samples) > self.streams:
             raise ValueError(f'a tick carries at most one frame per stream: {len(samples)} frames, {self.streams} streams')
-        streams, fids, seen, ori = [], [], set(), None
-        for sm in samples:
-            meta = sm.metainfo
+        streams, fids, seen, metas = [], [], set(), [sm.metainfo for sm in samples]
+        for meta in metas:
             if 'stream' not in meta or 'frame_id' not in meta:
                 raise KeyError("every sample's metainfo needs 'stream' and 'frame_id'")
             s, f = int(meta['stream']), int(meta['frame_id'])
@@ -120,62 +111,10 @@ class MultiStreamTracker:
             if f < 0:
                 raise ValueError(f'stream {s}: frame_id must be >= 0, got {f}')
             seen.add(s)
-            if 'ori_shape' in meta:
-                o = tuple(int(v) for v in meta['ori_shape'][:2])
-                if ori is not None and o != ori:
-                    raise NotImplementedError('one batched launch plan needs a uniform ori_shape')
-                ori = o
             streams.append(s)
             fids.append(f)
+        shell_inputs.uniform_ori_shape(metas)
         return streams, fids
-
-    def _inputs(self, data):
-        """The preprocessor and the shell's view of its output (mot.OCSORT_Disparity.begin): img / second input / gt."""
-        from . import sgbm as _sgbm
-        from .mot import RawFrames
-        model = self.model
-        if model._pre_lazy:
-            data = model.data_preprocessor(data, False, lazy_raw=True)
-        else:
-            data = model.data_preprocessor(data, False)
-        inputs, samples = data['inputs'], data['data_samples']
-
-        def unwrap(t, name):
-            if t is None or isinstance(t, RawFrames):
-                return t
-            assert t.dim() == 5, f'The {name} must be 5D Tensor (N, T, C, H, W).'
-            assert t.size(1) == 1, 'one key frame per sample (T = 1)'
-            return t[:, 0]
-        img = unwrap(inputs['img'], 'img')
-        if len(img) != len(samples):
-            raise ValueError(f'{len(img)} frames for {len(samples)} samples')
-        if img.device.type != 'cuda':
-            raise RuntimeError('MultiStreamTracker runs on the HIP path only: inputs must be CUDA tensors')
-        disp_postp = inputs.get('disp_postp')
-        stereo = disp_postp is None
-        if stereo:
-            if model.stereo is None or inputs.get('right') is None:
-                raise KeyError("inputs need 'disp_postp', or 'right' with a stereo module configured")
-            second = unwrap(inputs['right'], 'right')
-        else:
-            second = unwrap(disp_postp, 'disp_postp')
-            if isinstance(second, RawFrames):
-                second = second.dense()[:, 0]
-        gt = unwrap(inputs.get('depth_postp'), 'depth_postp')
-        if isinstance(gt, RawFrames):
-            gt = gt.dense()[:, 0]
-        metas = [s.metainfo for s in samples]
-        pad_hw = img.pad_hw if isinstance(img, RawFrames) else tuple(img.shape[-2:])
-        ori = tuple(int(v) for v in metas[0].get('ori_shape', pad_hw)[:2])
-        for m in metas[1:]:
-            if tuple(int(v) for v in m.get('ori_shape', ori)[:2]) != ori:
-                raise NotImplementedError('one batched launch plan needs a uniform ori_shape')
-        if stereo and isinstance(model.stereo, _sgbm.StereoSGBM):
-            for m in metas:
-                if 'img_shape' in m and tuple(int(v) for v in m['img_shape'][:2]) != ori:
-                    raise NotImplementedError(f"StereoSGBM matches at the original resolution: img_shape "
-                                              f"{tuple(m['img_shape'][:2])} differs from ori_shape {ori}")
-        return img, second, gt, stereo, ori, samples
 
     # ---- device state ------------------------------------------------------------------------------------------------
     def _device_state(self, dev):
@@ -186,13 +125,13 @@ class MultiStreamTracker:
         slots = self.max_chunks * self.chunk
         nbytes = int(self.lib.st_stream_record_bytes(S, T, M))
         off_hdr = 8 * S * T
-        off_trk = off_hdr + 4 * S * _HDR
-        off_det = off_trk + 4 * S * T * _ROW
-        assert nbytes == off_det + 4 * S * M * _DET, 'tick record layout differs from include/stereotrack.h'
+        off_trk = off_hdr + 4 * S * records.STREAM_HDR_INTS
+        off_det = off_trk + 4 * S * T * records.STREAM_ROW.floats
+        assert nbytes == off_det + 4 * S * M * records.STREAM_DET_FLOATS, 'tick record layout differs from include/stereotrack.h'
         with torch.cuda.device(dev):
             d = dict(dev=dev, stream=torch.cuda.Stream(device=dev),
                      tracker=BatchedGpuTracker(S, self.max_tracks, T, device=dev, **self.tracker_options),
-                     dets=torch.zeros(S, T, 8, dtype=torch.float32, device=dev),
+                     dets=torch.zeros(S, T, records.REC_FLOATS, dtype=torch.float32, device=dev),
                      counts=torch.full((S,), -1, dtype=torch.int32, device=dev),
                      fids=torch.full((S,), -1, dtype=torch.int32, device=dev),
                      boxes=torch.zeros(slots, T, 4, dtype=torch.float32, device=dev),
@@ -207,10 +146,13 @@ class MultiStreamTracker:
 
     # ---- submit: everything of a tick enqueued, no host wait ---------------------------------------------------------
     def _submit(self, data):
-        from .mot import RawFrames
         model = self.model
         streams, fids = self._routing(data)
-        img, second, gt, stereo, ori, samples = self._inputs(data)
+        data = shell_inputs.preprocess(model, data)
+        inputs, samples = data['inputs'], data['data_samples']
+        if len(inputs['img']) != len(samples):
+            raise ValueError(f"{len(inputs['img'])} frames for {len(samples)} samples")
+        img, second, gt, stereo, ori = shell_inputs.plan_inputs(model, inputs, samples, 'MultiStreamTracker')
         if self._pending > self.ahead:
             raise RuntimeError(f'{self._pending} ticks are already in flight: collect one before submitting another')
         n, B, S = len(samples), self.chunk, self.streams
@@ -228,15 +170,7 @@ class MultiStreamTracker:
         jobs = []
         for ci in range(nc):
             s, e = ci * B, min(n, ci * B + B)
-            a = b = None
-            if model.raw_stem and isinstance(img, RawFrames):
-                if stereo and isinstance(second, RawFrames):
-                    a, b = img.raw_chunk(s, e, B, runner), second.raw_chunk(s, e, B, runner)
-                elif not stereo:
-                    a = img.raw_chunk(s, e, B, runner)
-                    b = model._padded(second, s, e, B) if a is not None else None
-            if a is None or b is None:
-                a, b = model._padded(img, s, e, B), model._padded(second, s, e, B)
+            a, b = shell_inputs.chunk_inputs(model, img, second, stereo, s, e, B, runner)
             job = dict(s=s, e=e)
 
             def post(out, ctx, job=job):      # under the context's stream: the chunk's frame records, a tensor of their own
@@ -271,7 +205,7 @@ class MultiStreamTracker:
                 depth.append(model._box_depth(job['disp'], bx, bc, model.baseline, model.focal_length)[0])
                 if gt is not None:
                     gt.record_stream(A)
-                    gt_depth.append(model._box_depth(model._padded(gt, job['s'], job['e'], B), bx, bc, -1.0, 1.0)[0])
+                    gt_depth.append(model._box_depth(shell_inputs.padded(gt, job['s'], job['e'], B), bx, bc, -1.0, 1.0)[0])
             read = torch.cuda.Event()
             read.record(A)
             for job in jobs:                      # the disparity buffers may be rewritten once their depth has been read
@@ -300,9 +234,9 @@ class MultiStreamTracker:
         off_hdr, off_trk, off_det = d['offsets']
         raw = st['host'].numpy()
         ids = raw[:off_hdr].view(np.int64).reshape(S, T)
-        hdr = raw[off_hdr:off_trk].view(np.int32).reshape(S, _HDR)
-        trk = raw[off_trk:off_det].view(np.float32).reshape(S, T, _ROW)
-        det = raw[off_det:].view(np.float32).reshape(S, M, _DET)
+        hdr = raw[off_hdr:off_trk].view(np.int32).reshape(S, records.STREAM_HDR_INTS)
+        trk = raw[off_trk:off_det].view(np.float32).reshape(S, T, records.STREAM_ROW.floats)
+        det = raw[off_det:].view(np.float32).reshape(S, M, records.STREAM_DET_FLOATS)
         outs, bad = [], []
         for sample, s in zip(st['samples'], st['streams']):
             m, k, status, _ = (int(v) for v in hdr[s])
@@ -313,19 +247,10 @@ class MultiStreamTracker:
                 raise DetectionOverflow(f'stream {s}: {k} detections kept but the detection buffer has {M} rows; '
                                         f'build the model with a larger max_det')
             # copies: the page-locked buffer is reused a few ticks later
-            rows = torch.from_numpy(det[s, :k].copy())
-            dets = InstanceData(bboxes=rows[:, 0:4], scores=rows[:, 4],
-                                labels=torch.from_numpy(det[s, :k, 5].astype(np.int64)),
-                                prior_idx=torch.from_numpy(det[s, :k, 6].astype(np.int64)))
-            tr = torch.from_numpy(trk[s, :m].copy())
-            tracks = InstanceData()
-            tracks['bboxes'] = tr[:, 0:4]
-            tracks['labels'] = torch.from_numpy(trk[s, :m, 5].astype(np.int64))
-            tracks['scores'] = tr[:, 4]
-            tracks['scales'] = tr[:, 6]
-            tracks['depth'] = tr[:, 7].clone()
-            tracks['gt_depth'] = tr[:, 8].clone()
-            tracks.instances_id = torch.from_numpy(ids[s, :m].copy())
+            dets = records.detections(torch.from_numpy(det[s, :k].copy()), records.int_column(det[s, :k], records.LABEL),
+                                      records.int_column(det[s, :k], records.STREAM_DET_PRIOR))
+            tracks = records.tracks(torch.from_numpy(trk[s, :m].copy()), records.int_column(trk[s, :m], records.LABEL),
+                                    torch.from_numpy(ids[s, :m].copy()), records.STREAM_ROW)
             if model.results_device == 'input':
                 dets, tracks = dets.to(st['dev']), tracks.to(st['dev'])
             sample.pred_det_instances = dets

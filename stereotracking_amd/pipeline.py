@@ -13,7 +13,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, records
 from ._lib import check, current_stream, ptr
 from .engine import HipDetector, RawChunk, _require_cuda
 from .stereo import StereoCostVolume
@@ -29,6 +29,18 @@ def depth_method_code(name):
     if not isinstance(name, str) or name not in DEPTH_METHODS:
         raise ValueError(f'unknown depth extraction method {name!r}: one of {", ".join(DEPTH_METHODS)}')
     return DEPTH_METHODS[name]
+
+
+def launch_box_depth(lib, disp, boxes, counts, baseline, focal, method, out, channel_stride):
+    """ONE st_box_depth launch (st_box_depth_method for method != 0) on the current stream: disp (N,C,H,W) fp32, frames
+    `channel_stride` floats apart, boxes (N,M,4), counts (N,) -> out = (depth, scales, scaled boxes), every row defined."""
+    N, M = boxes.shape[0], boxes.shape[1]
+    args = (ptr(disp), channel_stride, N, *disp.shape[-2:], ptr(boxes), ptr(counts), M, float(baseline), float(focal),
+            None, 0, current_stream(), *(ptr(t) for t in out))
+    if method == 0:
+        check(lib.st_box_depth(*args), 'st_box_depth')
+    else:
+        check(lib.st_box_depth_method(*args, method), 'st_box_depth_method')
 
 
 def committed_tuning_plans():
@@ -288,15 +300,11 @@ class StereoDensePipeline:
     def box_depth(self, disp_postp, boxes, counts, out=None):
         """bbox_postp_depth (ocsort_disparity.py:113-130) on device -> depth, scales, scaled boxes."""
         b = self._buffers(disp_postp.device)
-        N, M = boxes.shape[0], boxes.shape[1]
-        depth, scales, sboxes = out if out is not None else (b['depth'], b['scales'], b['scaled_boxes'])
-        args = (ptr(disp_postp), 3 * self.height * self.width, N, self.height, self.width, ptr(boxes), ptr(counts), M,
-                self.baseline, self.focal_length, None, 0, current_stream(), ptr(depth), ptr(scales), ptr(sboxes))
-        if self._depth_code == 0:
-            check(self.lib.st_box_depth(*args), 'st_box_depth')
-        else:
-            check(self.lib.st_box_depth_method(*args, self._depth_code), 'st_box_depth_method')
-        return depth, scales, sboxes
+        out = out if out is not None else (b['depth'], b['scales'], b['scaled_boxes'])
+        _, Cc, H, W = disp_postp.shape      # the plan's (3, height, width): ONE source for the stride and the launch's H, W
+        launch_box_depth(self.lib, disp_postp, boxes, counts, self.baseline, self.focal_length, self._depth_code, out,
+                         Cc * H * W)
+        return out
 
     def run(self, img, right=None, disp_postp=None):
         """img (N,3,H,W) fp32 CUDA; stereo: right (N,3,H,W); mono: disp_postp (N,3,H,W).  img (and, stereo, right)
@@ -346,7 +354,7 @@ class StereoDensePipeline:
         Frames >= n_real are batch padding."""
         mode = 2 if scaled == 'both' else (1 if scaled is True else 0)
         N, M = out['boxes'].shape[0], out['boxes'].shape[1]
-        rec = torch.empty(N, M + 1, 13 if mode == 2 else 8, dtype=torch.float32, device=out['boxes'].device)
+        rec = torch.empty(N, M + 1, records.REC_FLOATS_BOTH if mode == 2 else records.REC_FLOATS, dtype=torch.float32, device=out['boxes'].device)
         check(_lib.load().st_pack_records(ptr(out['boxes']), ptr(out['scores']), ptr(out['labels']), ptr(out['depth']),
                                           ptr(out['scales']), ptr(out['scaled_boxes']), ptr(out['prior_idx']),
                                           ptr(out['counts']), N, M, mode, N if n_real is None else int(n_real),

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import records as _records
 from . import cmc as _cmc
 from .registry import MODELS
 from .structures import InstanceData
@@ -188,11 +189,7 @@ class OCSORTTracker_Disparity:
     # ---- native backend --------------------------------------------------------------------------
     def _handle(self):
         if self._native is None:
-            cfg = _lib.StTrackerConfig(C.sizeof(_lib.StTrackerConfig), float(self.obj_score_thr),
-                                       float(self.init_track_thr), int(bool(self.weight_iou_with_det_scores)),
-                                       float(self.match_iou_thr), int(self.num_tentatives),
-                                       float(self.vel_consist_weight), int(self.vel_delta_t),
-                                       int(self.num_frames_retain))
+            cfg = _lib.tracker_config(**{k: getattr(self, k) for k in _lib.TRACKER_OPTIONS})
             h = C.c_void_p()
             _lib.check(_lib.load().st_tracker_create(C.byref(cfg), C.byref(h)), 'st_tracker_create')
             self._native = h
@@ -227,7 +224,7 @@ class OCSORTTracker_Disparity:
         F, R, Cc = records.shape
         rec = np.ascontiguousarray(records, dtype=np.float32) if isinstance(records, np.ndarray) else records.numpy()
         fid = np.ascontiguousarray(frame_ids, dtype=np.int32)
-        rows = np.zeros((F, R - 1, 8), np.float32)     # rows past a frame's count stay zero (they are sliced off)
+        rows = np.zeros((F, R - 1, _records.TRACK_ROW.floats), np.float32)     # rows past a frame's count stay zero
         ids = np.zeros((F, R - 1), np.int64)
         counts = np.empty(F, np.int32)
         if self.with_cmc:
@@ -271,14 +268,14 @@ class OCSORTTracker_Disparity:
         det = data_sample.pred_det_instances
         dev = det.bboxes.device
         n = len(det.bboxes)
-        rows = np.empty((n, 8), np.float32)
-        rows[:, 0:4] = det.bboxes.detach().cpu().numpy()
-        rows[:, 4] = det.scores.detach().cpu().numpy()
+        rows = np.empty((n, _records.REC_FLOATS), np.float32)
+        rows[:, _records.BOX] = det.bboxes.detach().cpu().numpy()
+        rows[:, _records.SCORE] = det.scores.detach().cpu().numpy()
         labels = det.labels.detach().cpu()
-        rows[:, 5] = labels.numpy()
-        rows[:, 6] = det.depth.detach().cpu().numpy()
-        rows[:, 7] = det.scales.detach().cpu().numpy()
-        out = np.empty((n, 8), np.float32)
+        rows[:, _records.LABEL] = labels.numpy()
+        rows[:, _records.REC_DEPTH] = det.depth.detach().cpu().numpy()
+        rows[:, _records.REC_SCALE] = det.scales.detach().cpu().numpy()
+        out = np.empty((n, _records.TRACK_ROW.floats), np.float32)
         ids = np.empty(n, np.int64)
         k = C.c_int()
         frame_id = int(data_sample.metainfo.get('frame_id', -1))
@@ -301,14 +298,11 @@ class OCSORTTracker_Disparity:
         k = k.value
         self.num_tracks = int(_lib.load().st_tracker_next_id(self._native))
         t = torch.from_numpy(out[:k])
-        res = InstanceData()
-        res['bboxes'] = t[:, 0:4].contiguous().to(dev)
-        res['labels'] = t[:, 5].to(labels.dtype).to(dev)
-        res['scores'] = t[:, 4].contiguous().to(dev)
-        res['scales'] = t[:, 7].contiguous().to(dev)
-        res['depth'] = t[:, 6].contiguous().to(dev)
-        res.instances_id = torch.from_numpy(ids[:k]).to(labels.dtype).to(dev)
-        return res
+        col = lambda c: t[:, c].contiguous().to(dev)  # noqa: E731
+        return InstanceData(bboxes=col(_records.BOX), labels=t[:, _records.LABEL].to(labels.dtype).to(dev),
+                            scores=col(_records.SCORE), scales=col(_records.TRACK_ROW.scale),
+                            depth=col(_records.TRACK_ROW.depth),
+                            instances_id=torch.from_numpy(ids[:k]).to(labels.dtype).to(dev))
 
     @property
     def confirmed_ids(self):

@@ -399,3 +399,30 @@ def test_ticks_with_a_single_present_stream(cuda):
     plan = list(sched.ticks())
     assert len(plan) == 24 and all(len(p) == 1 for _, p in plan)
     assert run_and_compare(mst, sched, ref) == 24
+
+
+# ---- 7. ragged chunks through the cast-and-pad branch ---------------------------------------------------------------
+def test_ragged_chunks_without_the_raw_stem(cuda, monkeypatch):
+    """raw_stem off, S = 3 over dense_batch = 2: a tick of three frames ends in a ragged chunk, padded by repeating its
+    frame, and every chunk is cast + padded in a pass of its own (shell_inputs.chunk_inputs' second branch, which the
+    other tests here, with the raw stem on, never reach).  Stream 1 is absent in tick 2.  Equal to the alone runs."""
+    from stereotracking_amd.shell_inputs import RawFrames
+    calls = dict(chunk=0, raw_chunk=0)
+    for name in calls:
+        def spy(self, *args, _name=name, _orig=getattr(RawFrames, name)):
+            calls[_name] += 1
+            return _orig(self, *args)
+        monkeypatch.setattr(RawFrames, name, spy)
+    model, _, _ = build_model(CFG_STEREO, cuda, autotune=False)
+    model.dense_batch, model.raw_stem = 2, False
+    fo = lambda seeds: tiny_frames(seeds, cuda, False)     # noqa: E731
+    sched = Schedule([video(A[:4], fo), video(B_[:4], fo, skip=(2,)), video(D_[:4], fo)])
+    assert sched.num_ticks == 4 and [len(s) for s in sched.streams] == [4, 3, 4]
+    ref = sched.alone(model)
+    assert all(sum(len(o.pred_track_instances) for o in outs) > 0 for outs in ref)
+    mst = MultiStreamTracker(model, streams=3, max_tracks=TINY_MAX_TRACKS)
+    assert (mst.chunk, mst.max_chunks) == (2, 2)
+    calls.update(chunk=0, raw_chunk=0)
+    assert run_and_compare(mst, sched, ref) == 11
+    # 3 + 3 + 2 + 3 frames = 2 + 2 + 1 + 2 chunks, left and right converted for each; no chunk went to the stems raw
+    assert calls == dict(chunk=14, raw_chunk=0)
