@@ -832,6 +832,92 @@ int st_stream_record(const StStreamTick* tick, const float* rows_dev, const int6
                      void* record_dev, st_stream_t stream);
 
 /* ----------------------------------------------------------------------
+ * 15. MOT evaluation (MOTDroneMetrics: CLEAR, Identity, HOTA) on the device, csrc/mot_eval.hip.  The rules are the
+ *     statements of stereotracking_amd/metrics.py (clear_identity, hota); DESIGN.md section 15 lists what runs where.
+ *     fp64 and integer counts throughout, no floating-point atomics: two runs give the same bits.
+ *   rows     B sequences packed.  gt_rows (num_gt, 6) / pred_rows (num_pred, 6) fp64 = (frame number, DENSE id index
+ *            in [0, ng) / [0, nt) of the row's sequence, x, y, w, h), grouped by sequence, sorted by frame.
+ *   tables   built by the host (stereotracking_amd/mot_eval.py pack_sequences) and TRUSTED to be consistent:
+ *            seq_frame_off (B + 1) first global frame of every sequence; the frames of a sequence are the union of
+ *            its gt and prediction frames, ascending; frame_seq (F) sequence of a frame; frame_no (F) frame numbers;
+ *            frame_gt_off / frame_pred_off (F + 1) first row of every frame; frame_pair_off (F + 1) first cell of the
+ *            frame's G x P similarity matrix; seq_ng / seq_nt (B) id counts; seq_gid_off / seq_tid_off / seq_mat_off
+ *            (B + 1) first element of a sequence's per-gt-id, per-tracker-id and ng x nt arrays (ragged).
+ *            alphas (num_alphas <= ST_MOT_MAX_ALPHAS) fp64, passed from the host, never recomputed.
+ *   limits   at most st_mot_max_objects() = ST_MOT_MAX_OBJECTS rows of either kind in one frame.  A frame above it
+ *            sets status bit 8 and, with max_frame_objects filled in, st_mot_similarity returns ST_ERR_INVALID after
+ *            launching the checks.  The number of ids per sequence is bounded by the workspace only.
+ *   status   8 ints on the device, 0 = fine.  [0] bits: 1 non-finite box, 2 an id twice in one frame, 4 rows that are
+ *            not sorted (a row's frame number is not its frame's, or frame numbers do not ascend), 8 a frame above the
+ *            per-frame limit, 16 a dense id outside its sequence's range.  [1 + k] for bit 1 << k: num_frames - the
+ *            global frame index of the first offender.  Non-zero: the later stages return at once, outputs are not valid.
+ *   outputs  gt_count (sum ng) / tr_count (sum nt) ints; id_potential (sum ng nt) ints, frames with IoU >= iou_thr - eps;
+ *            hota_potential (sum ng nt) fp64, bit-equal to the host's per-frame +=; gt_frames / gt_matched / gt_frag
+ *            (sum ng) ints (MT / PT / ML / Frag bookkeeping); clear_counts (B, 4) TP FN FP IDSW; motp_sum (B);
+ *            hota_counts (B, num_alphas, 3) TP FN FP; hota_sums (B, num_alphas, 4) = sum of IoU over the TPs and the
+ *            AssA / AssRe / AssPr sums BEFORE the division by max(1, TP).  Identity's one global assignment, the
+ *            divisions and the combination over videos stay on the host.
+ *   Four stages, each enqueued on `stream`, launch count independent of the number of frames, no host wait:
+ *   st_mot_similarity (checks, IoU, row / column sums), st_mot_walk (flags ST_MOT_CLEAR | ST_MOT_HOTA: counts, both
+ *   potentials, CLEAR's matching in frame order, one wave per sequence), st_mot_hota_match (one assignment per frame),
+ *   st_mot_hota_accumulate (per sequence and alpha).  ws: caller-owned, st_mot_workspace_bytes(args), shared.
+ *   Order: st_mot_similarity first; st_mot_walk needs it and reads nothing a later stage writes, so it may be repeated
+ *   (for another flags value) at any point after it; st_mot_hota_match needs st_mot_walk with ST_MOT_HOTA (the
+ *   potential and the id counts), st_mot_hota_accumulate needs st_mot_hota_match.
+ * ---------------------------------------------------------------------- */
+#define ST_MOT_MAX_OBJECTS 256
+#define ST_MOT_MAX_ALPHAS 32
+#define ST_MOT_CLEAR 1
+#define ST_MOT_HOTA 2
+typedef struct StMotArgs {
+  int struct_size;              /* sizeof(StMotArgs) */
+  int num_seqs, num_frames, num_gt, num_pred, num_alphas;
+  int max_frame_objects;        /* host's knowledge of the largest frame (0: unknown) */
+  int flags;                    /* ST_MOT_CLEAR | ST_MOT_HOTA: what st_mot_walk accumulates */
+  long long num_pairs;          /* frame_pair_off[F] */
+  long long num_cells;          /* seq_mat_off[B] */
+  long long num_gids, num_tids; /* seq_gid_off[B], seq_tid_off[B] */
+  double iou_thr;
+  const double* gt_rows;
+  const double* pred_rows;
+  const int* seq_frame_off;
+  const int* frame_seq;
+  const long long* frame_no;
+  const int* frame_gt_off;
+  const int* frame_pred_off;
+  const long long* frame_pair_off;
+  const int* seq_ng;
+  const int* seq_nt;
+  const long long* seq_gid_off;
+  const long long* seq_tid_off;
+  const long long* seq_mat_off;
+  const double* alphas;
+  void* ws;
+  size_t ws_bytes;
+  int* gt_count;
+  int* tr_count;
+  int* id_potential;
+  double* hota_potential;
+  int* gt_frames;
+  int* gt_matched;
+  int* gt_frag;
+  int* clear_counts;
+  double* motp_sum;
+  int* hota_counts;
+  double* hota_sums;
+  int* status;
+} StMotArgs;
+int st_mot_max_objects(void);
+int st_mot_max_alphas(void);
+size_t st_mot_workspace_bytes(const StMotArgs* args);
+/* byte offset of the similarity matrices (num_pairs fp64, frame f at frame_pair_off[f], row-major G x P) inside ws */
+size_t st_mot_workspace_sim_offset(const StMotArgs* args);
+int st_mot_similarity(const StMotArgs* args, st_stream_t stream);
+int st_mot_walk(const StMotArgs* args, st_stream_t stream);
+int st_mot_hota_match(const StMotArgs* args, st_stream_t stream);
+int st_mot_hota_accumulate(const StMotArgs* args, st_stream_t stream);
+
+/* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call
  * (mmtrack/datasets/transforms/loading_disparity.py:74-75 uint16 disparity, :213-215 uint16 depth; mmcv's

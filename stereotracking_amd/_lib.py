@@ -86,6 +86,17 @@ class StCocoArgs(C.Structure):
                                    'status')]
 
 
+class StMotArgs(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('struct_size', 'num_seqs', 'num_frames', 'num_gt', 'num_pred', 'num_alphas',
+                                       'max_frame_objects', 'flags')] + \
+        [(n, C.c_longlong) for n in ('num_pairs', 'num_cells', 'num_gids', 'num_tids')] + [('iou_thr', C.c_double)] + \
+        [(n, C.c_void_p) for n in ('gt_rows', 'pred_rows', 'seq_frame_off', 'frame_seq', 'frame_no', 'frame_gt_off',
+                                   'frame_pred_off', 'frame_pair_off', 'seq_ng', 'seq_nt', 'seq_gid_off', 'seq_tid_off',
+                                   'seq_mat_off', 'alphas', 'ws')] + [('ws_bytes', C.c_size_t)] + \
+        [(n, C.c_void_p) for n in ('gt_count', 'tr_count', 'id_potential', 'hota_potential', 'gt_frames', 'gt_matched',
+                                   'gt_frag', 'clear_counts', 'motp_sum', 'hota_counts', 'hota_sums', 'status')]
+
+
 class StStreamTick(C.Structure):
     _fields_ = [('struct_size', C.c_int), ('streams', C.c_int), ('chunk', C.c_int), ('num_chunks', C.c_int),
                 ('max_dets', C.c_int), ('det_rows', C.c_int), ('stream_of_slot', C.c_void_p), ('frame_ids', C.c_void_p)]
@@ -222,6 +233,14 @@ _PROTOS = {
     'st_coco_prepare': (_i, [C.POINTER(StCocoArgs), _vp]),
     'st_coco_match': (_i, [C.POINTER(StCocoArgs), _vp]),
     'st_coco_accumulate': (_i, [C.POINTER(StCocoArgs), _vp]),
+    'st_mot_max_objects': (_i, []),
+    'st_mot_max_alphas': (_i, []),
+    'st_mot_workspace_bytes': (_sz, [C.POINTER(StMotArgs)]),
+    'st_mot_workspace_sim_offset': (_sz, [C.POINTER(StMotArgs)]),
+    'st_mot_similarity': (_i, [C.POINTER(StMotArgs), _vp]),
+    'st_mot_walk': (_i, [C.POINTER(StMotArgs), _vp]),
+    'st_mot_hota_match': (_i, [C.POINTER(StMotArgs), _vp]),
+    'st_mot_hota_accumulate': (_i, [C.POINTER(StMotArgs), _vp]),
     'st_box_depth_method': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _i]),
     'st_stream_record_bytes': (_sz, [_i, _i, _i]),
     'st_stream_gather': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp, _vp]),

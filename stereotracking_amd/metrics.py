@@ -34,9 +34,27 @@ def box_iou_xywh(a, b):
     return np.where(union > 0, inter / np.maximum(union, 1e-12), 0.0)
 
 
-def clear_identity(gt_rows, pred_rows, iou_thr=0.5):
+BACKENDS = ('host', 'device')
+
+
+def _check_backend(backend):
+    if backend not in BACKENDS:
+        raise ValueError(f'backend must be one of {BACKENDS}, got {backend!r}')
+
+
+def _device_single(gt_rows, pred_rows, iou_thr, metrics):
+    """One sequence through the device backend (stereotracking_amd/mot_eval.py)."""
+    from . import mot_eval
+    return mot_eval.evaluate_packed(mot_eval.pack_sequences([gt_rows], [pred_rows]), iou_thr, metrics)[0]
+
+
+def clear_identity(gt_rows, pred_rows, iou_thr=0.5, backend='host'):
     """gt_rows / pred_rows: arrays of (frame, id, x, y, w, h, ...).  Returns a dict with the CLEAR counts
-    (TP, FN, FP, IDSW, MOTA, MOTP) and Identity scores (IDTP, IDFN, IDFP, IDF1, IDP, IDR)."""
+    (TP, FN, FP, IDSW, MOTA, MOTP) and Identity scores (IDTP, IDFN, IDFP, IDF1, IDP, IDR).
+    backend='device': the same dict from the HIP path (mot_eval.py); raises without the library or a device."""
+    _check_backend(backend)
+    if backend == 'device':
+        return _device_single(gt_rows, pred_rows, iou_thr, ('CLEAR', 'Identity'))['clear_identity']
     gt_rows = np.asarray(gt_rows, dtype=np.float64)
     pred_rows = np.asarray(pred_rows, dtype=np.float64)
     if gt_rows.size == 0:
@@ -92,6 +110,13 @@ def clear_identity(gt_rows, pred_rows, iou_thr=0.5):
         fn += len(g) - len(rows)
         fp += len(p) - len(rows)
         motp_sum += float(sim[rows, cols].sum())
+    return _clear_identity_result(tp, fn, fp, idsw, motp_sum, potential, gt_count, tr_count, gt_frames, gt_matched, gt_frag)
+
+
+def _clear_identity_result(tp, fn, fp, idsw, motp_sum, potential, gt_count, tr_count, gt_frames, gt_matched, gt_frag):
+    """The result dict from a sequence's accumulated counts (either backend's): Identity's global assignment, the
+    MT / PT / ML / Frag bookkeeping and the ratios."""
+    ng, nt = len(gt_count), len(tr_count)
     # identity: one global assignment minimising IDFN + IDFP
     fn_mat = np.zeros((ng + nt, ng + nt))
     fp_mat = np.zeros((ng + nt, ng + nt))
@@ -123,7 +148,7 @@ def clear_identity(gt_rows, pred_rows, iou_thr=0.5):
 HOTA_ALPHAS = np.arange(0.05, 0.99, 0.05)     # 19 localisation thresholds 0.05 .. 0.95
 
 
-def hota(gt_rows, pred_rows):
+def hota(gt_rows, pred_rows, backend='host'):
     """HOTA of ONE sequence (Luiten et al., "HOTA: A Higher Order Metric for Evaluating Multi-Object Tracking", IJCV 2021;
     reference mot_drone_metrics.py:291-295 reports the averages over alpha of HOTA / AssA / DetA).  gt_rows / pred_rows:
     arrays of (frame, id, x, y, w, h, ...); similarity = box IoU.  Returns per-alpha arrays HOTA_TP / HOTA_FN / HOTA_FP,
@@ -132,7 +157,11 @@ def hota(gt_rows, pred_rows):
     Per alpha: a TP is a (gt, prediction) pair of one frame matched by the Hungarian assignment that maximises
     global_alignment(gt id, pred id) x IoU, kept if IoU >= alpha; DetA = TP / (TP + FN + FP);
     A(c) = TPA / (TPA + FNA + FPA) for a TP c with ids (g, p): TPA = TPs carrying the same id pair, FNA / FPA = the
-    other detections of g / p; AssA = mean of A over the TPs; HOTA = sqrt(DetA x AssA)."""
+    other detections of g / p; AssA = mean of A over the TPs; HOTA = sqrt(DetA x AssA).
+    backend='device': the same dict from the HIP path (mot_eval.py); raises without the library or a device."""
+    _check_backend(backend)
+    if backend == 'device':
+        return _device_single(gt_rows, pred_rows, 0.5, ('HOTA',))['hota']
     gt_rows = np.asarray(gt_rows, dtype=np.float64).reshape(-1, np.shape(gt_rows)[-1] if np.size(gt_rows) else 6)
     pred_rows = np.asarray(pred_rows, dtype=np.float64).reshape(-1, np.shape(pred_rows)[-1] if np.size(pred_rows) else 6)
     A = len(HOTA_ALPHAS)
@@ -220,7 +249,10 @@ class MOTDroneMetrics:
 
     allowed_metrics = ('HOTA', 'CLEAR', 'Identity')
 
-    def __init__(self, depth_thr=80, ignore_depth=False, iou_thr=0.5, metric=('HOTA', 'CLEAR', 'Identity')):
+    def __init__(self, depth_thr=80, ignore_depth=False, iou_thr=0.5, metric=('HOTA', 'CLEAR', 'Identity'),
+                 backend='host'):
+        _check_backend(backend)       # 'device': all videos in one mot_eval.evaluate_packed call, at evaluate()
+        self.backend = backend
         self.depth_thr, self.ignore_depth, self.iou_thr = depth_thr, ignore_depth, iou_thr
         self.metrics = [metric] if isinstance(metric, str) else list(metric)      # mot_drone_metrics.py:83-103
         for m in self.metrics:
@@ -298,8 +330,15 @@ class MOTDroneMetrics:
         return self._evaluate_local()
 
     def _evaluate_local(self):
-        per_video = {v: clear_identity(self.gt.get(v, []), self.pred.get(v, []), self.iou_thr)
-                     for v in sorted(set(self.gt) | set(self.pred))}
+        videos = sorted(set(self.gt) | set(self.pred))
+        if self.backend == 'device':
+            from . import mot_eval
+            packed = mot_eval.pack_sequences({v: self.gt.get(v, []) for v in videos}, {v: self.pred.get(v, []) for v in videos})
+            wanted = ['CLEAR', 'Identity'] + (['HOTA'] if 'HOTA' in self.metrics else [])
+            scored = dict(zip(packed['videos'], mot_eval.evaluate_packed(packed, self.iou_thr, wanted)))
+            per_video = {v: scored[v]['clear_identity'] for v in videos}
+        else:
+            per_video = {v: clear_identity(self.gt.get(v, []), self.pred.get(v, []), self.iou_thr) for v in videos}
         tot = defaultdict(float)
         for r in per_video.values():
             for k in ('TP', 'FN', 'FP', 'IDSW', 'IDTP', 'IDFN', 'IDFP'):
@@ -314,7 +353,8 @@ class MOTDroneMetrics:
         for k in ('Frag', 'MT', 'PT', 'ML'):
             combined[k] = float(sum(r[k] for r in per_video.values()))
         if 'HOTA' in self.metrics:      # mot_drone_metrics.py:291-295: the averages over the 19 thresholds
-            hs = {v: hota(self.gt.get(v, []), self.pred.get(v, [])) for v in per_video}
+            hs = {v: scored[v]['hota'] for v in per_video} if self.backend == 'device' else \
+                {v: hota(self.gt.get(v, []), self.pred.get(v, [])) for v in per_video}
             for v, h in hs.items():
                 per_video[v].update(HOTA=float(h['HOTA'].mean()), DetA=float(h['DetA'].mean()), AssA=float(h['AssA'].mean()))
             hc = hota_combine(hs.values()) if hs else _hota_final({k: np.zeros(len(HOTA_ALPHAS)) for k in

@@ -1,0 +1,363 @@
+"""MOT evaluation on the device: CLEAR, Identity and HOTA of many sequences in one call (csrc/mot_eval.hip behind
+st_mot_similarity / st_mot_walk / st_mot_hota_match / st_mot_hota_accumulate; include/stereotrack.h section 15).
+
+The rules are those of stereotracking_amd/metrics.py (clear_identity, hota), the executable specification; this module
+returns the same dictionaries.  The host keeps what is small or does not suit a wave: the sort
+and id compaction of the rows (pack_sequences, numpy), Identity's one global assignment per sequence (scipy, fed with
+the device's integer arrays), the final divisions and the combination over videos.
+
+    packed = pack_sequences(gt_by_video, pred_by_video)        # numpy only, no GPU needed
+    results = evaluate_packed(packed, iou_thr=0.5)             # one upload, one wait, one copy back
+    results[i]['clear_identity'], results[i]['hota']           # what metrics.clear_identity / metrics.hota return
+
+Both backends are defined up to ties of the assignment optimum ("Ties").
+"""
+import collections
+import ctypes as C
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import StMotArgs, check, current_stream
+
+ST_MOT_CLEAR, ST_MOT_HOTA = 1, 2
+STATUS_KINDS = ((1, 'a non-finite box'), (2, 'an id that occurs twice in one frame'), (4, 'rows that are not sorted by frame'),
+                (8, 'more objects in one frame than a launch holds'), (16, 'an id index outside its sequence'))
+LAUNCHES = collections.Counter()     # calls of every st_mot_* stage entry (tests read it)
+_TABLES = ('seq_frame_off', 'frame_seq', 'frame_no', 'frame_gt_off', 'frame_pred_off', 'frame_pair_off', 'seq_ng',
+           'seq_nt', 'seq_gid_off', 'seq_tid_off', 'seq_mat_off')
+
+
+def max_frame_objects():
+    """Largest number of ground-truth (or prediction) rows in one frame that a launch supports."""
+    return int(_lib.load().st_mot_max_objects())
+
+
+def _rows6(rows):
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.size == 0:
+        return np.zeros((0, 6))
+    return rows.reshape(-1, rows.shape[-1])[:, :6]
+
+
+def _sort_and_compact(rows, video, kind):
+    """rows sorted by frame (stable), ids replaced by their index in sorted(set(ids)); the frame numbers and the ids."""
+    frames = rows[:, 0].astype(np.int64)
+    order = np.argsort(frames, kind='stable')
+    rows, frames = rows[order], frames[order]
+    ids = rows[:, 1].astype(np.int64)
+    uniq = np.unique(ids)
+    dense = np.searchsorted(uniq, ids)
+    if len(rows) > 1:
+        o = np.lexsort((dense, frames))
+        same = (frames[o][1:] == frames[o][:-1]) & (dense[o][1:] == dense[o][:-1])
+        if same.any():
+            k = o[1:][np.argmax(same)]
+            raise ValueError(f'video {video!r}: {kind} id {int(ids[k])} occurs twice in frame {int(frames[k])}')
+    out = np.empty((len(rows), 6))
+    out[:, 0], out[:, 1], out[:, 2:] = frames, dense, rows[:, 2:6]
+    return out, frames, uniq
+
+
+def pack_sequences(gt_by_video, pred_by_video):
+    """The host preparation (pure numpy).  gt_by_video / pred_by_video: dicts video -> rows (frame, id, x, y, w, h, ...),
+    or two lists of equal length; a video missing on one side has no rows there.  Per video: rows sorted by frame, the
+    frames = the ascending union of both sides' frame numbers, ids compacted to their index in sorted(set(ids)) as the
+    host scorer does, and the ragged offset tables of include/stereotrack.h section 15.  An id twice in one frame
+    raises ValueError naming the video and the frame.  Returns a dict of arrays ('videos': the order)."""
+    if not isinstance(gt_by_video, dict):
+        gt_by_video = dict(enumerate(gt_by_video))
+    if not isinstance(pred_by_video, dict):
+        pred_by_video = dict(enumerate(pred_by_video))
+    videos = sorted(set(gt_by_video) | set(pred_by_video))
+    gt_parts, pr_parts, frame_no, frame_seq, fg, fp_ = [], [], [], [], [0], [0]
+    seq_frame_off, seq_ng, seq_nt, gt_ids, tr_ids = [0], [], [], [], []
+    ngt = npr = 0
+    for s, v in enumerate(videos):
+        g, gfr, gu = _sort_and_compact(_rows6(gt_by_video.get(v, ())), v, 'ground-truth')
+        p, pfr, pu = _sort_and_compact(_rows6(pred_by_video.get(v, ())), v, 'prediction')
+        frames = np.union1d(gfr, pfr)
+        gt_parts.append(g)
+        pr_parts.append(p)
+        frame_no.append(frames)
+        frame_seq.append(np.full(len(frames), s, np.int32))
+        fg.append(ngt + np.searchsorted(gfr, frames, 'right'))
+        fp_.append(npr + np.searchsorted(pfr, frames, 'right'))
+        ngt, npr = ngt + len(g), npr + len(p)
+        seq_frame_off.append(seq_frame_off[-1] + len(frames))
+        seq_ng.append(len(gu))
+        seq_nt.append(len(pu))
+        gt_ids.append(gu)
+        tr_ids.append(pu)
+    if max(ngt, npr, seq_frame_off[-1]) >= 2 ** 31 - 1:
+        raise ValueError(f'pack_sequences: {ngt} ground-truth rows, {npr} prediction rows, {seq_frame_off[-1]} frames: the '
+                         f'offset tables are 32-bit')
+    out = dict(videos=videos, gt_ids=gt_ids, tr_ids=tr_ids)
+    out['gt_rows'] = np.ascontiguousarray(np.concatenate(gt_parts)) if videos else np.zeros((0, 6))
+    out['pred_rows'] = np.ascontiguousarray(np.concatenate(pr_parts)) if videos else np.zeros((0, 6))
+    out['seq_frame_off'] = np.asarray(seq_frame_off, np.int32)
+    out['frame_seq'] = np.concatenate(frame_seq + [np.zeros(0, np.int32)]).astype(np.int32)
+    out['frame_no'] = np.concatenate(frame_no + [np.zeros(0, np.int64)]).astype(np.int64)
+    out['frame_gt_off'] = np.concatenate([np.atleast_1d(a) for a in fg]).astype(np.int32)
+    out['frame_pred_off'] = np.concatenate([np.atleast_1d(a) for a in fp_]).astype(np.int32)
+    G, P = np.diff(out['frame_gt_off']).astype(np.int64), np.diff(out['frame_pred_off']).astype(np.int64)
+    out['frame_pair_off'] = np.concatenate([[0], np.cumsum(G * P)]).astype(np.int64)
+    out['seq_ng'], out['seq_nt'] = np.asarray(seq_ng, np.int32), np.asarray(seq_nt, np.int32)
+    ng, nt = out['seq_ng'].astype(np.int64), out['seq_nt'].astype(np.int64)
+    out['seq_gid_off'] = np.concatenate([[0], np.cumsum(ng)]).astype(np.int64)
+    out['seq_tid_off'] = np.concatenate([[0], np.cumsum(nt)]).astype(np.int64)
+    out['seq_mat_off'] = np.concatenate([[0], np.cumsum(ng * nt)]).astype(np.int64)
+    out['max_frame_objects'] = int(max(G.max(initial=0), P.max(initial=0)))
+    return out
+
+
+class _Layout:
+    """Arrays side by side in one byte buffer, every one at a multiple of 256 bytes."""
+
+    def __init__(self):
+        self.items, self.size = {}, 0
+
+    def add(self, name, shape, dtype):
+        dtype = np.dtype(dtype)
+        n = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
+        self.items[name] = (self.size, tuple(int(v) for v in shape), dtype)
+        self.size += (n + 255) // 256 * 256 + 256
+
+    def view(self, buf, name):
+        off, shape, dtype = self.items[name]
+        n = int(np.prod(shape, dtype=np.int64))
+        return buf[off:off + n * dtype.itemsize].view(dtype).reshape(shape)
+
+
+def _where(packed, status, kind):
+    f = int(packed['frame_no'].shape[0]) - int(status[1 + kind])
+    return packed['videos'][int(packed['frame_seq'][f])], int(packed['frame_no'][f])
+
+
+def _raise_status(packed, status):
+    bits = int(status[0])
+    for kind, (bit, what) in enumerate(STATUS_KINDS):
+        if bits & bit:
+            video, frame = _where(packed, status, kind)
+            msg = f'MOT evaluation: {what}: video {video!r}, frame {frame}'
+            if bit == 8:
+                msg += f' (at most {max_frame_objects()} ground-truth and {max_frame_objects()} prediction rows per frame)'
+            raise ValueError(msg) if bit in (1, 2, 8) else _lib.StError(msg)
+    raise _lib.StError(f'MOT evaluation failed on the device: status {bits}')
+
+
+def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None, alphas=None, timing=False,
+                    return_arrays=False):
+    """Scores every sequence of `packed` (pack_sequences) on the device.  Returns one dict per sequence, in the order of
+    packed['videos']: 'clear_identity' = what metrics.clear_identity returns ('CLEAR' or 'Identity' in `metrics`, else
+    None), 'hota' = what metrics.hota returns, per-alpha arrays included ('HOTA' in `metrics`, else None: the HOTA
+    stages are then not launched).  One upload, one wait and one copy back per call, however many sequences.
+    `timing`: returns (results, timing dict) - HIP events around every stage and the host clock of the parts of the
+    call.  `return_arrays`: every dict also carries 'arrays' with the
+    device's intermediates of that sequence (sim: the IoU matrix of every frame, hota_potential, id_potential,
+    gt_count, tr_count) - one extra copy of the workspace, for tests."""
+    from . import metrics as M
+    t_start = time.perf_counter()
+    metrics = [metrics] if isinstance(metrics, str) else list(metrics)
+    do_hota = 'HOTA' in metrics
+    do_clear = 'CLEAR' in metrics or 'Identity' in metrics
+    if not (do_hota or do_clear):
+        raise ValueError(f'evaluate_packed: nothing to compute for metrics {metrics}')
+    if not torch.cuda.is_available():
+        raise RuntimeError('the device backend of the MOT evaluation runs on the HIP path only (csrc/mot_eval.hip) and '
+                           'no CUDA (ROCm) device is available; use backend=\'host\'')
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise RuntimeError(f'the device backend of the MOT evaluation needs a CUDA (ROCm) device, got {dev}')
+    alphas = np.ascontiguousarray(M.HOTA_ALPHAS if alphas is None else alphas, dtype=np.float64)
+    B, F, A = len(packed['videos']), len(packed['frame_no']), len(alphas)
+    if B == 0:
+        return []
+    NG, NP_ = len(packed['gt_rows']), len(packed['pred_rows'])
+    ids_g, ids_t, cells = int(packed['seq_gid_off'][-1]), int(packed['seq_tid_off'][-1]), int(packed['seq_mat_off'][-1])
+
+    # ---- one upload
+    lin = _Layout()
+    host_in = dict(gt_rows=packed['gt_rows'], pred_rows=packed['pred_rows'], alphas=alphas, **{k: packed[k] for k in _TABLES})
+    for k, v in host_in.items():
+        lin.add(k, v.shape, v.dtype)
+    hbuf = np.zeros(lin.size, np.uint8)
+    for k, v in host_in.items():
+        lin.view(hbuf, k)[...] = v
+    t_prep = time.perf_counter()
+    dbuf = torch.from_numpy(hbuf).to(dev)
+
+    lout = _Layout()
+    for name, shape, dt in (('status', (8,), np.int32), ('gt_count', (ids_g,), np.int32), ('tr_count', (ids_t,), np.int32),
+                            ('id_potential', (cells,), np.int32), ('hota_potential', (cells,), np.float64),
+                            ('gt_frames', (ids_g,), np.int32), ('gt_matched', (ids_g,), np.int32),
+                            ('gt_frag', (ids_g,), np.int32), ('clear_counts', (B, 4), np.int32),
+                            ('motp_sum', (B,), np.float64), ('hota_counts', (B, A, 3), np.int32),
+                            ('hota_sums', (B, A, 4), np.float64)):
+        lout.add(name, shape, dt)
+    obuf = torch.zeros(lout.size, dtype=torch.uint8, device=dev)
+
+    args = StMotArgs()
+    args.struct_size = C.sizeof(StMotArgs)
+    args.num_seqs, args.num_frames, args.num_gt, args.num_pred, args.num_alphas = B, F, NG, NP_, A
+    args.max_frame_objects = int(packed['max_frame_objects'])
+    args.flags = (ST_MOT_CLEAR if do_clear else 0) | (ST_MOT_HOTA if do_hota else 0)
+    args.num_pairs, args.num_cells, args.num_gids, args.num_tids = int(packed['frame_pair_off'][-1]), cells, ids_g, ids_t
+    args.iou_thr = float(iou_thr)
+    for k in host_in:
+        setattr(args, k, C.c_void_p(dbuf.data_ptr() + lin.items[k][0]))
+    for k in lout.items:
+        setattr(args, k, C.c_void_p(obuf.data_ptr() + lout.items[k][0]))
+    args.ws, args.ws_bytes = None, 0
+    nbytes = int(lib.st_mot_workspace_bytes(C.byref(args)))
+    if nbytes == 0:
+        raise _lib.StError('st_mot_workspace_bytes: invalid sizes')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    args.ws, args.ws_bytes = C.c_void_p(ws.data_ptr()), nbytes
+
+    stages = [('st_mot_similarity', lib.st_mot_similarity), ('st_mot_walk', lib.st_mot_walk)]
+    if do_hota:
+        stages += [('st_mot_hota_match', lib.st_mot_hota_match), ('st_mot_hota_accumulate', lib.st_mot_hota_accumulate)]
+    over_limit = False
+    with torch.cuda.device(dev):
+        stream = current_stream()
+        events = [torch.cuda.Event(enable_timing=True) for _ in range(len(stages) + 1)] if timing else None
+        for i, (name, fn) in enumerate(stages):
+            if timing:
+                events[i].record()
+            LAUNCHES[name] += 1
+            rc = fn(C.byref(args), stream)
+            if name == 'st_mot_similarity' and rc == -1 and args.max_frame_objects > max_frame_objects():
+                over_limit = True      # the checks were launched: the status word names the frame
+                break
+            check(rc, name)
+        if timing and not over_limit:
+            events[-1].record()
+    host = obuf.cpu().numpy()          # the one wait and the one copy back
+    t_back = time.perf_counter()
+    status = lout.view(host, 'status')
+    if status[0] or over_limit:
+        _raise_status(packed, status)
+    o = {k: lout.view(host, k) for k in lout.items}
+    sim = None
+    if return_arrays:
+        off = int(lib.st_mot_workspace_sim_offset(C.byref(args)))
+        sim = ws[off:off + 8 * args.num_pairs].cpu().numpy().view(np.float64)
+
+    results = []
+    for s in range(B):
+        ng, nt = int(packed['seq_ng'][s]), int(packed['seq_nt'][s])
+        g0, t0, m0 = int(packed['seq_gid_off'][s]), int(packed['seq_tid_off'][s]), int(packed['seq_mat_off'][s])
+        f0, f1 = int(packed['seq_frame_off'][s]), int(packed['seq_frame_off'][s + 1])
+        n_gt = int(packed['frame_gt_off'][f1] - packed['frame_gt_off'][f0])
+        n_pr = int(packed['frame_pred_off'][f1] - packed['frame_pred_off'][f0])
+        gt_count = o['gt_count'][g0:g0 + ng].astype(np.float64)
+        tr_count = o['tr_count'][t0:t0 + nt].astype(np.float64)
+        res = dict(clear_identity=None, hota=None)
+        if do_clear:
+            tp, fn, fp, idsw = (int(v) for v in o['clear_counts'][s])
+            res['clear_identity'] = M._clear_identity_result(
+                tp, fn, fp, idsw, float(o['motp_sum'][s]), o['id_potential'][m0:m0 + ng * nt].reshape(ng, nt).astype(np.float64),
+                gt_count, tr_count, *(o[k][g0:g0 + ng].astype(np.float64) for k in ('gt_frames', 'gt_matched', 'gt_frag')))
+        if do_hota:
+            h = {k: np.zeros(A) for k in ('HOTA_TP', 'HOTA_FN', 'HOTA_FP', 'AssA', 'AssRe', 'AssPr', 'LocA')}
+            if n_gt == 0 or n_pr == 0:        # metrics.hota's early return
+                h['HOTA_FN'] += n_gt
+                h['HOTA_FP'] += n_pr
+                h['LocA'] += 1.0
+            else:
+                cnt, sums = o['hota_counts'][s], o['hota_sums'][s]
+                h['HOTA_TP'] += cnt[:, 0]
+                h['HOTA_FN'] += cnt[:, 1]
+                h['HOTA_FP'] += cnt[:, 2]
+                tp = np.maximum(1.0, h['HOTA_TP'])
+                h['AssA'], h['AssRe'], h['AssPr'] = sums[:, 1] / tp, sums[:, 2] / tp, sums[:, 3] / tp
+                h['LocA'] = np.maximum(1e-10, sums[:, 0]) / np.maximum(1e-10, h['HOTA_TP'])
+            res['hota'] = M._hota_final(h)
+        if return_arrays:
+            po = packed['frame_pair_off']
+            G, P = np.diff(packed['frame_gt_off']), np.diff(packed['frame_pred_off'])
+            res['arrays'] = dict(sim=[sim[po[f]:po[f + 1]].reshape(G[f], P[f]).copy() for f in range(f0, f1)],
+                                 hota_potential=o['hota_potential'][m0:m0 + ng * nt].reshape(ng, nt).copy(),
+                                 id_potential=o['id_potential'][m0:m0 + ng * nt].reshape(ng, nt).copy(),
+                                 gt_count=o['gt_count'][g0:g0 + ng].copy(), tr_count=o['tr_count'][t0:t0 + nt].copy())
+        results.append(res)
+    if timing:
+        t_end = time.perf_counter()
+        return results, dict(stages_ms={name: events[i].elapsed_time(events[i + 1]) for i, (name, _) in enumerate(stages)},
+                             host_prepare_s=t_prep - t_start, device_and_copies_s=t_back - t_prep,
+                             host_finish_s=t_end - t_back, total_s=t_end - t_start)
+    return results
+
+
+class TrackCollector:
+    """Collects the per-step outputs of a BatchedGpuTracker run on the device and brings them to the host with ONE
+    device-to-host copy per run (to_host), not one per step."""
+
+    def __init__(self):
+        self.frames, self._rows, self._ids, self._n = [], [], [], []
+
+    def add(self, frame_ids, rows, ids, n):
+        """frame_ids: the step's frame number of every sequence (host ints); rows / ids / n: what step() returned
+        (the tracker reuses these buffers, so they are copied, device to device)."""
+        self.frames.append(np.asarray(frame_ids, dtype=np.int64).reshape(-1))
+        self._rows.append(rows.detach().clone())
+        self._ids.append(ids.detach().clone())
+        self._n.append(n.detach().clone())
+
+    def to_host(self):
+        """-> frames (T, B), rows (T, B, M, row floats) float32, ids (T, B, M) int64, n (T, B) int32."""
+        rows, ids, n = torch.stack(self._rows), torch.stack(self._ids), torch.stack(self._n)
+        parts = [t.contiguous().view(torch.uint8).reshape(-1) for t in (ids, rows, n)]
+        flat = torch.cat(parts).cpu().numpy()          # the run's one device-to-host copy
+        a, b = parts[0].numel(), parts[0].numel() + parts[1].numel()
+        return (np.stack(self.frames), flat[a:b].view(np.float32).reshape(tuple(rows.shape)),
+                flat[:a].view(np.int64).reshape(tuple(ids.shape)), flat[b:].view(np.int32).reshape(tuple(n.shape)))
+
+    def prediction_rows(self):
+        """One (R, 6) fp64 array per sequence: (frame, id, x, y, w, h) of every output row, in step order, in IMAGE
+        space: the tracker's rows carry depth-scaled boxes, which are scaled back about their centres by 1 / scale
+        (the row's scale column) with the fp32 operations of mot.scale_bbox, as every product path does before a box is
+        reported or scored.  The ground truth they are scored against is the image-space one MOTDroneMetrics uses."""
+        from .records import TRACK_ROW
+        two = np.float32(2.0)
+        frames, rows, ids, n = self.to_host()
+        T, B = n.shape
+        out = []
+        for b in range(B):
+            parts = []
+            for t in range(T):
+                k = int(n[t, b])
+                if k <= 0:
+                    continue
+                r = rows[t, b, :k]
+                inv = np.float32(1.0) / r[:, TRACK_ROW.scale]
+                cx, cy = (r[:, 0] + r[:, 2]) / two, (r[:, 1] + r[:, 3]) / two
+                w, h = (r[:, 2] - r[:, 0]) * inv, (r[:, 3] - r[:, 1]) * inv
+                box = np.stack([cx - w / two, cy - h / two, cx + w / two, cy + h / two], 1).astype(np.float64)
+                parts.append(np.column_stack([np.full(k, frames[t, b], np.float64), ids[t, b, :k].astype(np.float64),
+                                              box[:, 0], box[:, 1], box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]]))
+            out.append(np.concatenate(parts) if parts else np.zeros((0, 6)))
+        return out
+
+
+def evaluate_sweep(predictions, gt, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None, backend='device'):
+    """Scores the B prediction sets of a batched tracker run (a TrackCollector, or a list of B row arrays) against one
+    ground-truth row array (shared) or a list of B of them.  Returns B dicts as evaluate_packed does.  A collector's
+    rows are scaled back to image space (TrackCollector.prediction_rows), so the ground truth is the image-space one;
+    row arrays passed directly are scored as they are.
+    backend='host' scores the same rows with metrics.clear_identity / metrics.hota (the reference of the tests)."""
+    preds = predictions.prediction_rows() if isinstance(predictions, TrackCollector) else list(predictions)
+    gts = list(gt) if isinstance(gt, (list, tuple)) else [gt] * len(preds)
+    if len(gts) != len(preds):
+        raise ValueError(f'evaluate_sweep: {len(preds)} prediction sets against {len(gts)} ground-truth sets')
+    if backend == 'host':
+        from . import metrics as M
+        return [dict(clear_identity=M.clear_identity(g, p, iou_thr), hota=M.hota(g, p) if 'HOTA' in metrics else None)
+                for g, p in zip(gts, preds)]
+    if backend != 'device':
+        raise ValueError(f"evaluate_sweep: backend must be 'host' or 'device', got {backend!r}")
+    return evaluate_packed(pack_sequences(gts, preds), iou_thr, metrics, device)
