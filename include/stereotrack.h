@@ -918,6 +918,59 @@ int st_mot_hota_match(const StMotArgs* args, st_stream_t stream);
 int st_mot_hota_accumulate(const StMotArgs* args, st_stream_t stream);
 
 /* ----------------------------------------------------------------------
+ * 16. KITTI 2-D box preprocessing (MOTKittiMetrics) on the device, csrc/mot_eval.hip.  The rules are the statements of
+ *     stereotracking_amd/metrics.py kitti_preprocess: per frame and evaluated class one
+ *     assignment between the ground truth of the class or its distractors and the predictions of the class; matched
+ *     predictions on a distractor / occluded / truncated object and unmatched ones that are too small or inside an
+ *     ignore region are removed; the ground truth kept is that of the class within the occlusion / truncation limits.
+ *     fp64 and integers throughout, no atomics on the outputs, one launch: two runs give the same bytes.
+ *   rows     all sequences packed, sorted by sequence and frame.  gt_rows (num_gt, 9) fp64 = (frame, id, class,
+ *            truncation, occlusion, x1, y1, x2, y2); pred_rows (num_pred, 8) = (frame, id, class, x1, y1, x2, y2,
+ *            score); ignore_rows (num_ignore, 5) = (frame, x1, y1, x2, y2).  Only class, truncation, occlusion and the
+ *            boxes are read.
+ *   tables   built by the host (stereotracking_amd/mot_eval.py kitti_keep_masks) and TRUSTED: frame_gt_off /
+ *            frame_pred_off / frame_ignore_off (num_frames + 1) first row of every frame; frame_ws_off (num_frames + 1,
+ *            64-bit) first cell of the frame's slot in ws: a frame whose rows of all classes make more than 64 x 64
+ *            cells needs a slot of (gt rows) x (prediction rows) cells, any other frame may have an empty one (smaller
+ *            matrices are solved out of LDS); num_ws_cells = frame_ws_off[num_frames].  class_table (num_classes, 5)
+ *            int32: the class id, then up to 4 distractor ids, unused entries -1.
+ *   consts   max_occlusion, max_truncation, min_height, match_thr (IoU of a match), ignore_thr (intersection over the
+ *            prediction's area with an ignore region); eps = 2^-52 is added / subtracted as kitti_preprocess does.
+ *   limits   at most ST_MOT_MAX_OBJECTS ground-truth rows of a class and its distractors, and as many prediction rows
+ *            of the class, in one frame; more rows of other classes may share the frame.
+ *   status   8 ints, 0 = fine, zeroed by the call.  [0] bits: 1 non-finite box (any row of the frame), 8 a frame above
+ *            the limit, 32 a frame whose ws slot is too small.  [1 + k] for bit 1 << k: num_frames - the frame index
+ *            of the first offender.  The frames that set a bit write nothing.
+ *   outputs  gt_keep (num_classes, num_gt) / pred_keep (num_classes, num_pred) bytes, 1 = the row is scored for that
+ *            class.  Both are zeroed by the call, so a row of another class holds 0.
+ *   One stage, enqueued on `stream`, one kernel launch (one wave per frame and class), no host wait.
+ *   ws: caller-owned, st_mot_kitti_workspace_bytes(args) (0: invalid sizes).
+ * ---------------------------------------------------------------------- */
+#define ST_MOT_KITTI_MAX_DISTRACTORS 4
+typedef struct StMotKittiArgs {
+  int struct_size;              /* sizeof(StMotKittiArgs) */
+  int num_frames, num_classes, num_gt, num_pred, num_ignore;
+  int max_frame_objects;        /* largest number of gt or prediction rows (all classes) in one frame; 0: unknown */
+  long long num_ws_cells;       /* frame_ws_off[num_frames] */
+  double max_occlusion, max_truncation, min_height, match_thr, ignore_thr;
+  const double* gt_rows;
+  const double* pred_rows;
+  const double* ignore_rows;
+  const int* frame_gt_off;
+  const int* frame_pred_off;
+  const int* frame_ignore_off;
+  const long long* frame_ws_off;
+  const int* class_table;
+  void* ws;
+  size_t ws_bytes;
+  unsigned char* gt_keep;
+  unsigned char* pred_keep;
+  int* status;
+} StMotKittiArgs;
+size_t st_mot_kitti_workspace_bytes(const StMotKittiArgs* args);
+int st_mot_kitti_preprocess(const StMotKittiArgs* args, st_stream_t stream);
+
+/* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call
  * (mmtrack/datasets/transforms/loading_disparity.py:74-75 uint16 disparity, :213-215 uint16 depth; mmcv's

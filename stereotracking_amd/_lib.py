@@ -97,6 +97,15 @@ class StMotArgs(C.Structure):
                                    'gt_frag', 'clear_counts', 'motp_sum', 'hota_counts', 'hota_sums', 'status')]
 
 
+class StMotKittiArgs(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('struct_size', 'num_frames', 'num_classes', 'num_gt', 'num_pred', 'num_ignore',
+                                       'max_frame_objects')] + [('num_ws_cells', C.c_longlong)] + \
+        [(n, C.c_double) for n in ('max_occlusion', 'max_truncation', 'min_height', 'match_thr', 'ignore_thr')] + \
+        [(n, C.c_void_p) for n in ('gt_rows', 'pred_rows', 'ignore_rows', 'frame_gt_off', 'frame_pred_off',
+                                   'frame_ignore_off', 'frame_ws_off', 'class_table', 'ws')] + [('ws_bytes', C.c_size_t)] + \
+        [(n, C.c_void_p) for n in ('gt_keep', 'pred_keep', 'status')]
+
+
 class StStreamTick(C.Structure):
     _fields_ = [('struct_size', C.c_int), ('streams', C.c_int), ('chunk', C.c_int), ('num_chunks', C.c_int),
                 ('max_dets', C.c_int), ('det_rows', C.c_int), ('stream_of_slot', C.c_void_p), ('frame_ids', C.c_void_p)]
@@ -241,6 +250,8 @@ _PROTOS = {
     'st_mot_walk': (_i, [C.POINTER(StMotArgs), _vp]),
     'st_mot_hota_match': (_i, [C.POINTER(StMotArgs), _vp]),
     'st_mot_hota_accumulate': (_i, [C.POINTER(StMotArgs), _vp]),
+    'st_mot_kitti_workspace_bytes': (_sz, [C.POINTER(StMotKittiArgs)]),
+    'st_mot_kitti_preprocess': (_i, [C.POINTER(StMotKittiArgs), _vp]),
     'st_box_depth_method': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _i]),
     'st_stream_record_bytes': (_sz, [_i, _i, _i]),
     'st_stream_gather': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp, _vp]),

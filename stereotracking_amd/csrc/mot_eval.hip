@@ -14,7 +14,10 @@
 //   hota_accumulate  k_hota_acc     one workgroup per (sequence, alpha): TP / FN / FP, the IoU sum, the integer matches
 //                                   matrix (integer atomics) and the AssA / AssRe / AssPr sums
 //
-// One solver serves k_walk and k_hota_match: solve_assignment, the shortest-augmenting-path (Jonker-Volgenant /
+//   kitti_preprocess k_kitti        one wave per (frame, class): KITTI's 2-D box preprocessing behind st_mot_kitti_preprocess
+//                                   (section 16): class split by ballots, thresholded IoU, one assignment, the keep bytes
+//
+// One solver serves k_walk, k_hota_match and k_kitti: solve_assignment, the shortest-augmenting-path (Jonker-Volgenant /
 // Hungarian) method for one wave, exact on a rectangular matrix of non-negative fp64 weights.
 #include <climits>
 #include <cmath>
@@ -534,6 +537,168 @@ __global__ __launch_bounds__(kAccThreads) void k_hota_acc(StMotArgs a, Workspace
   }
 }
 
+// ---- KITTI 2-D box preprocessing (include/stereotrack.h section 16, metrics.py kitti_preprocess) ---------------------
+constexpr int kGtCols = 9, kPredCols = 8, kIgnCols = 5;        // row widths; the boxes start at columns 5, 3 and 1
+constexpr int kMaxDistractors = ST_MOT_KITTI_MAX_DISTRACTORS;
+constexpr int kWsSlot = 32;                                     // status bit: a frame's workspace slot is too small
+
+struct KittiBox { double x1, y1, x2, y2; };
+
+__device__ inline KittiBox load_box(const double* __restrict__ p) { return KittiBox{p[0], p[1], p[2], p[3]}; }
+
+__device__ inline bool finite_box(const double* __restrict__ p) {
+  return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && isfinite(p[3]);
+}
+
+// intersection and the two areas, in the operation order of TrackEval's _calculate_box_ious on x0y0x1y1 boxes
+__device__ inline double kitti_inter(const KittiBox& a, const KittiBox& b, double* a1, double* a2) {
+  double iw = fmin(a.x2, b.x2) - fmax(a.x1, b.x1);
+  double ih = fmin(a.y2, b.y2) - fmax(a.y1, b.y1);
+  iw = iw < 0.0 ? 0.0 : iw;
+  ih = ih < 0.0 ? 0.0 : ih;
+  *a1 = (a.x2 - a.x1) * (a.y2 - a.y1);
+  *a2 = (b.x2 - b.x1) * (b.y2 - b.y1);
+  return iw * ih;
+}
+
+// the rows of [s, e) that `pick` selects, in row order, as indices in list[0 .. kMaxObj); returns how many there are
+template <typename Pick>
+__device__ inline int compact_rows(int s, int e, int lane, int* list, Pick pick) {
+  int count = 0;
+  for (int base = s; base < e; base += 64) {
+    const int r = base + lane;
+    const bool in = r < e && pick(r);
+    const unsigned long long mask = __ballot(in);
+    const int pos = count + __popcll(mask & ((1ull << lane) - 1ull));
+    if (in && pos < kMaxObj) list[pos] = r;
+    count += __popcll(mask);
+  }
+  return count;
+}
+
+__global__ __launch_bounds__(64) void k_kitti(StMotKittiArgs a, double* ws, int lds_cells) {
+  SolverLds& S = *reinterpret_cast<SolverLds*>(mot_smem);
+  double* Wl = reinterpret_cast<double*>(mot_smem + kSolverBytes);
+  const int f = blockIdx.x / a.num_classes, ci = blockIdx.x - f * a.num_classes, lane = threadIdx.x;
+  const int rep = a.num_frames - f;
+  const int gs = a.frame_gt_off[f], ge = a.frame_gt_off[f + 1];
+  const int ps = a.frame_pred_off[f], pe = a.frame_pred_off[f + 1];
+  const int is = a.frame_ignore_off[f], ie = a.frame_ignore_off[f + 1];
+  if (gs < 0 || ge < gs || ge > a.num_gt || ps < 0 || pe < ps || pe > a.num_pred || is < 0 || ie < is || ie > a.num_ignore) {
+    if (lane == 0) report(a.status, kFrameLimit, 3, rep);      // an offset table that does not fit the row arrays
+    return;
+  }
+  bool bad = false;
+  for (int r = gs + lane; r < ge; r += 64) bad = bad || !finite_box(a.gt_rows + (size_t)kGtCols * r + 5);
+  for (int r = ps + lane; r < pe; r += 64) bad = bad || !finite_box(a.pred_rows + (size_t)kPredCols * r + 3);
+  for (int r = is + lane; r < ie; r += 64) bad = bad || !finite_box(a.ignore_rows + (size_t)kIgnCols * r + 1);
+  if (bad) report(a.status, kNonFinite, 0, rep);
+  if (__any(bad)) return;
+
+  const int* __restrict__ ct = a.class_table + (1 + kMaxDistractors) * ci;
+  const double cls = (double)ct[0];
+  double dis[kMaxDistractors];
+  for (int k = 0; k < kMaxDistractors; ++k) dis[k] = (double)ct[1 + k];
+  auto is_distractor = [&](double c) {
+    bool d = false;
+    for (int k = 0; k < kMaxDistractors; ++k) d = d || (ct[1 + k] >= 0 && c == dis[k]);
+    return d;
+  };
+  // step 1: G = the ground truth of the class or a distractor (S.gid), P = the predictions of the class (S.tid)
+  const int G = compact_rows(gs, ge, lane, S.gid, [&](int r) {
+    const double c = a.gt_rows[(size_t)kGtCols * r + 2];
+    return c == cls || is_distractor(c);
+  });
+  const int P = compact_rows(ps, pe, lane, S.tid, [&](int r) { return a.pred_rows[(size_t)kPredCols * r + 2] == cls; });
+  if (G > kMaxObj || P > kMaxObj) {
+    if (lane == 0) report(a.status, kFrameLimit, 3, rep);
+    return;
+  }
+  __syncthreads();
+  // step 5: the ground truth kept for scoring needs no matching
+  unsigned char* __restrict__ gt_keep = a.gt_keep + (size_t)ci * (size_t)a.num_gt;
+  unsigned char* __restrict__ pred_keep = a.pred_keep + (size_t)ci * (size_t)a.num_pred;
+  for (int i = lane; i < G; i += 64) {
+    const double* row = a.gt_rows + (size_t)kGtCols * S.gid[i];
+    if (row[2] == cls && row[4] <= a.max_occlusion && row[3] <= a.max_truncation) gt_keep[S.gid[i]] = 1;
+  }
+  // steps 2 and 3: the thresholded IoU matrix, one assignment; S.used[j]: 0 unmatched, 1 matched and kept, 2 removed
+  const int cells = G * P;
+  if (cells > 0) {
+    double* W = Wl;
+    if (cells > lds_cells) {
+      const long long w0 = a.frame_ws_off[f], w1 = a.frame_ws_off[f + 1];
+      if (w0 < 0 || w1 > a.num_ws_cells || w1 - w0 < (long long)cells) {
+        if (lane == 0) report(a.status, kWsSlot, 5, rep);
+        return;
+      }
+      W = ws + (size_t)ci * (size_t)a.num_ws_cells + (size_t)w0;
+    }
+    const double thr = a.match_thr - kEps;
+    for (int c = lane; c < cells; c += 64) {
+      const int i = c / P, j = c - i * P;
+      const KittiBox g = load_box(a.gt_rows + (size_t)kGtCols * S.gid[i] + 5);
+      const KittiBox p = load_box(a.pred_rows + (size_t)kPredCols * S.tid[j] + 3);
+      double a1, a2;
+      double inter = kitti_inter(g, p, &a1, &a2);
+      double uni = (a1 + a2) - inter;
+      if (a1 <= kEps || a2 <= kEps || uni <= kEps) inter = 0.0;
+      if (uni <= kEps) uni = 1.0;
+      const double sv = inter / uni;
+      W[c] = sv < thr ? 0.0 : sv;
+    }
+    __syncthreads();
+    solve_assignment(W, G, P, S, lane);
+    for (int j = lane; j < P; j += 64) S.used[j] = 0;
+    __syncthreads();
+    for (int i = lane; i < G; i += 64) {
+      const int j = S.mcol[i];
+      if (j < 0 || !(W[(size_t)i * P + j] > kEps)) continue;
+      const double* row = a.gt_rows + (size_t)kGtCols * S.gid[i];
+      const bool remove = is_distractor(row[2]) || row[4] > a.max_occlusion + kEps || row[3] > a.max_truncation + kEps;
+      S.used[j] = remove ? 2 : 1;      // the columns of an assignment are distinct
+    }
+    __syncthreads();
+  }
+  // step 4: the unmatched predictions
+  for (int j = lane; j < P; j += 64) {
+    const int r = S.tid[j];
+    const int state = cells > 0 ? S.used[j] : 0;
+    bool keep = state == 1;
+    if (state == 0) {
+      const KittiBox p = load_box(a.pred_rows + (size_t)kPredCols * r + 3);
+      bool removed = (p.y2 - p.y1) <= a.min_height + kEps;
+      for (int k = is; k < ie && !removed; ++k) {
+        const KittiBox g = load_box(a.ignore_rows + (size_t)kIgnCols * k + 1);
+        double a1, a2;
+        double inter = kitti_inter(p, g, &a1, &a2);
+        if (a1 <= kEps) { inter = 0.0; a1 = 1.0; }
+        removed = inter / a1 > a.ignore_thr + kEps;
+      }
+      keep = !removed;
+    }
+    if (keep) pred_keep[r] = 1;
+  }
+}
+
+int validate_kitti(const StMotKittiArgs* a) {
+  ST_REQUIRE(a != nullptr, "st_mot_kitti: args is NULL");
+  ST_REQUIRE(a->struct_size == (int)sizeof(StMotKittiArgs), "st_mot_kitti: struct_size %d != %d", a->struct_size,
+             (int)sizeof(StMotKittiArgs));
+  ST_REQUIRE(a->num_frames >= 0 && a->num_classes >= 1 && a->num_gt >= 0 && a->num_pred >= 0 && a->num_ignore >= 0,
+             "st_mot_kitti: num_frames %d / num_gt %d / num_pred %d / num_ignore %d must be >= 0, num_classes %d >= 1",
+             a->num_frames, a->num_gt, a->num_pred, a->num_ignore, a->num_classes);
+  ST_REQUIRE((long long)a->num_frames * a->num_classes < (1ll << 31) - 1, "st_mot_kitti: num_frames x num_classes too large");
+  ST_REQUIRE(a->num_ws_cells >= 0, "st_mot_kitti: num_ws_cells must be >= 0");
+  ST_REQUIRE(a->ws != nullptr && a->ws_bytes >= st_mot_kitti_workspace_bytes(a), "st_mot_kitti: workspace %zu < %zu bytes",
+             a->ws_bytes, st_mot_kitti_workspace_bytes(a));
+  ST_REQUIRE(a->status != nullptr && a->gt_keep != nullptr && a->pred_keep != nullptr,
+             "st_mot_kitti: status / gt_keep / pred_keep is NULL");
+  ST_REQUIRE(a->num_frames == 0 || (a->frame_gt_off && a->frame_pred_off && a->frame_ignore_off && a->frame_ws_off &&
+                                    a->class_table), "st_mot_kitti: an offset table or the class table is NULL");
+  return ST_OK;
+}
+
 int validate(const StMotArgs* a) {
   ST_REQUIRE(a != nullptr, "st_mot: args is NULL");
   ST_REQUIRE(a->struct_size == (int)sizeof(StMotArgs), "st_mot: struct_size %d != %d", a->struct_size,
@@ -643,6 +808,26 @@ int st_mot_hota_accumulate(const StMotArgs* a, st_stream_t stream_) {
   carve(a, a->ws, &w);
   ST_CHECK(zero(w.matches, 0, (size_t)a->num_cells * (size_t)a->num_alphas * sizeof(int), stream));
   hipLaunchKernelGGL(k_hota_acc, dim3(a->num_seqs * a->num_alphas), dim3(kAccThreads), 0, stream, *a, w);
+  ST_CHECK_HIP(hipGetLastError());
+  return ST_OK;
+}
+
+size_t st_mot_kitti_workspace_bytes(const StMotKittiArgs* args) {
+  if (!args || args->struct_size != (int)sizeof(StMotKittiArgs) || args->num_classes < 1 || args->num_ws_cells < 0) return 0;
+  return align256(((size_t)args->num_classes * (size_t)args->num_ws_cells + 1) * sizeof(double));
+}
+
+int st_mot_kitti_preprocess(const StMotKittiArgs* a, st_stream_t stream_) {
+  ST_CHECK(validate_kitti(a));
+  hipStream_t stream = (hipStream_t)stream_;
+  ST_CHECK(zero(a->status, 0, 8 * sizeof(int), stream));
+  ST_CHECK(zero(a->gt_keep, 0, (size_t)a->num_classes * (size_t)a->num_gt, stream));
+  ST_CHECK(zero(a->pred_keep, 0, (size_t)a->num_classes * (size_t)a->num_pred, stream));
+  const long long m = a->max_frame_objects;
+  const int lds_cells = m <= 0 ? 0 : (int)(m * m < kLdsCells ? m * m : kLdsCells);
+  if (a->num_frames > 0)
+    hipLaunchKernelGGL(k_kitti, dim3(a->num_frames * a->num_classes), dim3(64), kSolverBytes + lds_cells * sizeof(double),
+                       stream, *a, (double*)a->ws, lds_cells);
   ST_CHECK_HIP(hipGetLastError());
   return ST_OK;
 }

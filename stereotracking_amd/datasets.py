@@ -4,6 +4,8 @@ input pipeline consumes (uint8 pixels, uint16 disparity codes -> RawFrameUploade
 
 Mirrors, for the test-time path only:
   MOTDispDataset.parse_data_info        reference mmtrack/datasets/mot_disp_dataset.py:38-97 (paths, instance filter rules)
+  MOTKittiDataset.parse_data_info       mmtrack/datasets/mot_kitti_dataset.py:40-110 (KITTI Tracking: 'img2' path rewrite,
+                                        occluded_thr, the instance fields MOTKittiMetrics reads, cat2label)
   BaseVideoDataset._load_video_data_list  mmtrack/datasets/base_video_dataset.py:104-148 (CocoVID traversal, video_length)
   VideoSampler                          mmtrack/datasets/samplers/video_sampler.py:25-70 (whole videos per rank)
   LoadDisparityFromFile                 mmtrack/datasets/transforms/loading_disparity.py:71-134 (uint16, 65535 invalid, /16)
@@ -224,6 +226,56 @@ class MOTDispDataset:
         ends = self.video_first[1:] + [len(self.data_list)]
         names = [self.videos[v] for v in sorted(self.videos)]
         return [(n, list(range(a, b))) for n, a, b in zip(names, self.video_first, ends)]
+
+
+@DATASETS.register_module(name=['MOTKittiDataset', 'mmtrack.MOTKittiDataset'])
+class MOTKittiDataset(MOTDispDataset):
+    """KITTI Tracking view of the reference's MOTKittiDataset (mot_kitti_dataset.py:11-110) on the CocoVID traversal of
+    MOTDispDataset: the nine lower-case classes, paths made by replacing 'img2' in the file name (disp_path with
+    disparity_dir_name; right_path with right_dir_name is this project's addition, the reference never reads the right
+    image), the instance fields MOTKittiMetrics writes (:88-99) and cat2label in every data info (:105-110).
+    occluded_thr: outside test mode an annotation with `occluded` BELOW it is dropped (:68-70, as the reference has it)."""
+
+    METAINFO = {'CLASSES': ('car', 'van', 'truck', 'pedestrian', 'person', 'cyclist', 'tram', 'misc', 'dontcare')}
+
+    def __init__(self, ann_file, occluded_thr=2, detection_file=None, disparity_dir_name='disparity', right_dir_name='img3',
+                 **kwargs):
+        self.occluded_thr = occluded_thr
+        super().__init__(ann_file, disparity_dir_name=disparity_dir_name, right_dir_name=right_dir_name,
+                         detection_file=detection_file, **kwargs)
+
+    def parse_data_info(self, raw_data_info):
+        """mot_kitti_dataset.py:40-103, statement for statement in behaviour."""
+        img_info, ann_info = raw_data_info['raw_img_info'], raw_data_info['raw_ann_info']
+        info = dict(img_info)
+        fname = img_info['file_name']
+        prefix = self.data_prefix.get('img_path')
+        img_path = os.path.join(prefix, fname) if prefix is not None else fname
+        info['img_path'] = img_path
+        info['disp_path'] = img_path.replace(fname, fname.replace('img2', self.disparity_dir_name))
+        info['right_path'] = img_path.replace(fname, fname.replace('img2', self.right_dir_name))
+        instances = []
+        for ann in ann_info:
+            if (not self.test_mode) and ann['occluded'] < self.occluded_thr:
+                continue
+            if ann.get('ignore', False):
+                continue
+            x1, y1, w, h = ann['bbox']
+            inter_w = max(0, min(x1 + w, img_info['width']) - max(x1, 0))
+            inter_h = max(0, min(y1 + h, img_info['height']) - max(y1, 0))
+            if inter_w * inter_h == 0:
+                continue
+            if ann['area'] <= 0 or w < 1 or h < 1:
+                continue
+            if ann['category_id'] not in self.cat_ids:
+                continue
+            instances.append(dict(ignore_flag=1 if ann.get('iscrowd', False) else 0, instance_id=ann['instance_id'],
+                                  category_id=ann['category_id'], bbox_label=self.cat2label[ann['category_id']],
+                                  truncated=ann['truncated'], occluded=ann['occluded'], alpha=ann['alpha'],
+                                  bbox=[x1, y1, x1 + w, y1 + h], dim=ann['dim'], location=ann['location'],
+                                  rotation_y=ann['rotation_y'], mot_conf=ann['mot_conf'], visibility=ann['visibility']))
+        info['instances'] = instances
+        return info
 
 
 @DATA_SAMPLERS.register_module(name=['VideoSampler', 'mmtrack.VideoSampler'])

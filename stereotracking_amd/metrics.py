@@ -13,6 +13,9 @@ TrackEval computes them [upstream-memory]: CLEAR - per-frame Hungarian matching 
 previous frame's match; Identity - one global bipartite matching; HOTA - per-frame Hungarian matching that maximises
 (global alignment score x IoU), thresholded per alpha, association accuracy per matched pair from the id-pair counts.
 Parity is UNPINNED against TrackEval itself (absent); the known-answer tests are hand-derived from the definitions.
+
+KITTI Tracking (stereotracking_amd/kitti_metrics.py, MOTKittiMetrics): kitti_box_ious and kitti_preprocess restate the
+preprocessing TrackEval applies to KITTI's 2-D boxes before these scorers see a sequence [upstream-memory].
 """
 import os
 from collections import defaultdict
@@ -244,7 +247,141 @@ def hota_combine(per_sequence):
     return _hota_final(res)
 
 
-class MOTDroneMetrics:
+def kitti_box_ious(a, b, do_ioa=False):
+    """IoU of (n, 4) and (m, 4) boxes in x1, y1, x2, y2 form with the rules of TrackEval's _calculate_box_ious
+    [upstream-memory]: intersection clipped at 0, union = a1 + a2 - inter, intersection 0 where an area or the union is
+    <= eps, union 1 where it is <= eps.  do_ioa: the intersection over the area of `a` instead (0 where that area is
+    <= eps)."""
+    eps = np.finfo(float).eps
+    a, b = np.asarray(a, dtype=np.float64).reshape(-1, 4), np.asarray(b, dtype=np.float64).reshape(-1, 4)
+    lo = np.maximum(a[:, None, :2], b[None, :, :2])
+    hi = np.minimum(a[:, None, 2:], b[None, :, 2:])
+    inter = np.maximum(hi[..., 0] - lo[..., 0], 0) * np.maximum(hi[..., 1] - lo[..., 1], 0)
+    area1 = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    if do_ioa:
+        inter[area1 <= eps, :] = 0
+        return inter / np.where(area1 <= eps, 1.0, area1)[:, None]
+    area2 = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    union = area1[:, None] + area2[None, :] - inter
+    inter[area1 <= eps, :] = 0
+    inter[:, area2 <= eps] = 0
+    inter[union <= eps] = 0
+    union[union <= eps] = 1
+    return inter / union
+
+
+def kitti_preprocess(gt_rows, pred_rows, ignore_boxes, cls_id, distractor_ids, max_occlusion=2, max_truncation=0,
+                     min_height=25, match_thr=0.5, ignore_thr=0.5):
+    """KITTI's per-frame preprocessing of ONE sequence for ONE evaluated class: what TrackEval's
+    Kitti2DBox.get_preprocessed_seq_data does before a sequence is scored, restated from memory of that package
+    [upstream-memory] (the reference's Kitti2DBox_MOT, mmtrack/evaluation/functional/kitti_2d_box.py, inherits it and
+    fixes the constants, :56-58).  The executable specification of st_mot_kitti_preprocess.
+
+    gt_rows (frame, id, class, truncation, occlusion, x1, y1, x2, y2) without the DontCare rows, pred_rows (frame, id,
+    class, x1, y1, x2, y2, score), ignore_boxes (frame, x1, y1, x2, y2): the DontCare regions.  Per frame: one
+    assignment between the ground truth of class cls_id or a distractor and the predictions of class cls_id on the IoU
+    thresholded at match_thr; a matched prediction is removed when its partner is a distractor, occluded or truncated
+    beyond the limits; an unmatched one when it is not higher than min_height or lies more than ignore_thr inside an
+    ignore region.  Returns (gt_keep, pred_keep), boolean masks over the input rows: the rows scored for the class."""
+    eps = np.finfo(float).eps
+    gt_rows = np.asarray(gt_rows, dtype=np.float64).reshape(-1, 9)
+    pred_rows = np.asarray(pred_rows, dtype=np.float64).reshape(-1, 8)
+    ignore_boxes = np.asarray(ignore_boxes, dtype=np.float64).reshape(-1, 5)
+    distractor_ids = list(distractor_ids)
+    gt_keep = (gt_rows[:, 2] == cls_id) & (gt_rows[:, 4] <= max_occlusion) & (gt_rows[:, 3] <= max_truncation)
+    pred_keep = np.zeros(len(pred_rows), dtype=bool)
+    g_in = np.isin(gt_rows[:, 2], [cls_id] + distractor_ids)
+    p_in = pred_rows[:, 2] == cls_id
+    gf, pf, nf = gt_rows[:, 0].astype(np.int64), pred_rows[:, 0].astype(np.int64), ignore_boxes[:, 0].astype(np.int64)
+    for f in np.unique(pf[p_in]):
+        gi, pi = np.nonzero(g_in & (gf == f))[0], np.nonzero(p_in & (pf == f))[0]
+        g, p = gt_rows[gi], pred_rows[pi]
+        unmatched = np.ones(len(pi), dtype=bool)
+        removed = np.zeros(len(pi), dtype=bool)
+        if len(gi) and len(pi):
+            score = kitti_box_ious(g[:, 5:9], p[:, 3:7])
+            score[score < match_thr - eps] = 0
+            rows, cols = linear_sum_assignment(-score)
+            ok = score[rows, cols] > 0 + eps
+            rows, cols = rows[ok], cols[ok]
+            removed[cols] = np.isin(g[rows, 2], distractor_ids) | (g[rows, 4] > max_occlusion + eps) | \
+                (g[rows, 3] > max_truncation + eps)
+            unmatched[cols] = False
+        too_small = p[:, 6] - p[:, 4] <= min_height + eps
+        in_ignore = np.any(kitti_box_ious(p[:, 3:7], ignore_boxes[nf == f, 1:5], do_ioa=True) > ignore_thr + eps, axis=1)
+        removed |= unmatched & (too_small | in_ignore)
+        pred_keep[pi] = ~removed
+    return gt_keep, pred_keep
+
+
+def combine_videos(per_video, hota_by_video=None):
+    """The combined result over videos (count-summed, like TrackEval's COMBINED_SEQ) of per-video clear_identity
+    dicts.  hota_by_video: the videos' hota() dicts when HOTA is asked for (None: not asked); every video's dict then
+    gains its HOTA / DetA / AssA means over the 19 thresholds and the combined one those of hota_combine, with LocA."""
+    tot = defaultdict(float)
+    for r in per_video.values():
+        for k in ('TP', 'FN', 'FP', 'IDSW', 'IDTP', 'IDFN', 'IDFP'):
+            tot[k] += r[k]
+        tot['motp_sum'] += r['MOTP'] * r['TP']
+    combined = dict(tot)
+    combined['MOTA'] = (tot['TP'] - tot['FP'] - tot['IDSW']) / max(1.0, tot['TP'] + tot['FN'])
+    combined['MOTP'] = tot['motp_sum'] / max(1.0, tot['TP'])
+    combined['IDF1'] = tot['IDTP'] / max(1.0, tot['IDTP'] + 0.5 * tot['IDFP'] + 0.5 * tot['IDFN'])
+    combined['IDP'] = tot['IDTP'] / max(1.0, tot['IDTP'] + tot['IDFP'])
+    combined['IDR'] = tot['IDTP'] / max(1.0, tot['IDTP'] + tot['IDFN'])
+    for k in ('Frag', 'MT', 'PT', 'ML'):
+        combined[k] = float(sum(r[k] for r in per_video.values()))
+    if hota_by_video is not None:      # mot_drone_metrics.py:291-295: the averages over the 19 thresholds
+        hs = hota_by_video
+        for v, h in hs.items():
+            per_video[v].update(HOTA=float(h['HOTA'].mean()), DetA=float(h['DetA'].mean()), AssA=float(h['AssA'].mean()))
+        hc = hota_combine(hs.values()) if hs else _hota_final({k: np.zeros(len(HOTA_ALPHAS)) for k in
+                                                               ('HOTA_TP', 'HOTA_FN', 'HOTA_FP', 'AssA', 'AssRe', 'AssPr', 'LocA')})
+        combined.update(HOTA=float(hc['HOTA'].mean()), DetA=float(hc['DetA'].mean()), AssA=float(hc['AssA'].mean()),
+                        LocA=float(hc['LocA'].mean()))
+    return combined
+
+
+class GatheredVideoMetric:
+    """What the video metrics share: per-video row lists in self.pred / self.gt, merged over the ranks by gather(), and
+    evaluate() that lets rank 0 compute _evaluate_local() and broadcasts the result."""
+
+    def gather(self):
+        """Multi-rank evaluation, the reference's way (mot_drone_metrics.py:336-358: barrier, all_gather_object of the
+        per-video `seq_info`, rank 0 evaluates, broadcast_object_list of the result): ranks hold DISJOINT whole videos
+        (video_sampler.py:62-70 / dist.shard_videos), so the per-video row lists are merged by key.  Afterwards every
+        rank holds every video's rows.  No-op without an initialised process group."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return self
+        dist.barrier()                                   # wait for all processes to complete prediction (:336)
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, dict(pred=dict(self.pred), gt=dict(self.gt)))   # KBs of pickled rows (:340)
+        pred, gt = defaultdict(list), defaultdict(list)
+        for part in parts:                               # rank order = video order of shard_videos
+            for v, rows in part['pred'].items():
+                if v in pred:
+                    raise RuntimeError(f'video {v!r} was evaluated on more than one rank: videos shard whole')
+                pred[v] = rows
+            for v, rows in part['gt'].items():
+                gt[v] = rows
+        self.pred, self.gt = pred, gt
+        return self
+
+    def evaluate(self, distributed=True):
+        """Per-video and combined (count-summed, like TrackEval's COMBINED_SEQ) scores.  With a process group (and
+        `distributed`): gather first, rank 0 computes, every rank returns the broadcast result (:344-358)."""
+        import torch.distributed as dist
+        multi = distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        if multi:
+            self.gather()
+            box = [self._evaluate_local() if dist.get_rank() == 0 else None]
+            dist.broadcast_object_list(box, src=0)
+            return box[0]
+        return self._evaluate_local()
+
+
+class MOTDroneMetrics(GatheredVideoMetric):
     """Collects per-frame tracks, writes MOTChallenge files, scores them (depth-range filtered)."""
 
     allowed_metrics = ('HOTA', 'CLEAR', 'Identity')
@@ -295,40 +432,6 @@ class MOTDroneMetrics:
                 for t in rows:
                     f.write('%d,%d,%d,%d,%d,%d,%d,%d,%.5f\n' % tuple(t[:9]))
 
-    def gather(self):
-        """Multi-rank evaluation, the reference's way (mot_drone_metrics.py:336-358: barrier, all_gather_object of the
-        per-video `seq_info`, rank 0 evaluates, broadcast_object_list of the result): ranks hold DISJOINT whole videos
-        (video_sampler.py:62-70 / dist.shard_videos), so the per-video row lists are merged by key.  Afterwards every
-        rank holds every video's rows.  No-op without an initialised process group."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-            return self
-        dist.barrier()                                   # wait for all processes to complete prediction (:336)
-        parts = [None] * dist.get_world_size()
-        dist.all_gather_object(parts, dict(pred=dict(self.pred), gt=dict(self.gt)))   # KBs of pickled rows (:340)
-        pred, gt = defaultdict(list), defaultdict(list)
-        for part in parts:                               # rank order = video order of shard_videos
-            for v, rows in part['pred'].items():
-                if v in pred:
-                    raise RuntimeError(f'video {v!r} was evaluated on more than one rank: videos shard whole')
-                pred[v] = rows
-            for v, rows in part['gt'].items():
-                gt[v] = rows
-        self.pred, self.gt = pred, gt
-        return self
-
-    def evaluate(self, distributed=True):
-        """Per-video and combined (count-summed, like TrackEval's COMBINED_SEQ) scores.  With a process group (and
-        `distributed`): gather first, rank 0 computes, every rank returns the broadcast result (:344-358)."""
-        import torch.distributed as dist
-        multi = distributed and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        if multi:
-            self.gather()
-            box = [self._evaluate_local() if dist.get_rank() == 0 else None]
-            dist.broadcast_object_list(box, src=0)
-            return box[0]
-        return self._evaluate_local()
-
     def _evaluate_local(self):
         videos = sorted(set(self.gt) | set(self.pred))
         if self.backend == 'device':
@@ -339,26 +442,8 @@ class MOTDroneMetrics:
             per_video = {v: scored[v]['clear_identity'] for v in videos}
         else:
             per_video = {v: clear_identity(self.gt.get(v, []), self.pred.get(v, []), self.iou_thr) for v in videos}
-        tot = defaultdict(float)
-        for r in per_video.values():
-            for k in ('TP', 'FN', 'FP', 'IDSW', 'IDTP', 'IDFN', 'IDFP'):
-                tot[k] += r[k]
-            tot['motp_sum'] += r['MOTP'] * r['TP']
-        combined = dict(tot)
-        combined['MOTA'] = (tot['TP'] - tot['FP'] - tot['IDSW']) / max(1.0, tot['TP'] + tot['FN'])
-        combined['MOTP'] = tot['motp_sum'] / max(1.0, tot['TP'])
-        combined['IDF1'] = tot['IDTP'] / max(1.0, tot['IDTP'] + 0.5 * tot['IDFP'] + 0.5 * tot['IDFN'])
-        combined['IDP'] = tot['IDTP'] / max(1.0, tot['IDTP'] + tot['IDFP'])
-        combined['IDR'] = tot['IDTP'] / max(1.0, tot['IDTP'] + tot['IDFN'])
-        for k in ('Frag', 'MT', 'PT', 'ML'):
-            combined[k] = float(sum(r[k] for r in per_video.values()))
-        if 'HOTA' in self.metrics:      # mot_drone_metrics.py:291-295: the averages over the 19 thresholds
+        hs = None
+        if 'HOTA' in self.metrics:
             hs = {v: scored[v]['hota'] for v in per_video} if self.backend == 'device' else \
                 {v: hota(self.gt.get(v, []), self.pred.get(v, [])) for v in per_video}
-            for v, h in hs.items():
-                per_video[v].update(HOTA=float(h['HOTA'].mean()), DetA=float(h['DetA'].mean()), AssA=float(h['AssA'].mean()))
-            hc = hota_combine(hs.values()) if hs else _hota_final({k: np.zeros(len(HOTA_ALPHAS)) for k in
-                                                                   ('HOTA_TP', 'HOTA_FN', 'HOTA_FP', 'AssA', 'AssRe', 'AssPr', 'LocA')})
-            combined.update(HOTA=float(hc['HOTA'].mean()), DetA=float(hc['DetA'].mean()), AssA=float(hc['AssA'].mean()),
-                            LocA=float(hc['LocA'].mean()))
-        return dict(per_video=per_video, combined=combined)
+        return dict(per_video=per_video, combined=combine_videos(per_video, hs))

@@ -10,6 +10,11 @@ the device's integer arrays), the final divisions and the combination over video
     results = evaluate_packed(packed, iou_thr=0.5)             # one upload, one wait, one copy back
     results[i]['clear_identity'], results[i]['hota']           # what metrics.clear_identity / metrics.hota return
 
+KITTI's 2-D box preprocessing (metrics.kitti_preprocess, the specification; st_mot_kitti_preprocess, include/stereotrack.h
+section 16) runs ahead of them for MOTKittiMetrics(backend='device'):
+
+    masks = kitti_keep_masks(sequences, classes)               # one upload, one launch, one wait and copy back
+
 Both backends are defined up to ties of the assignment optimum ("Ties").
 """
 import collections
@@ -291,6 +296,143 @@ def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), 
                              host_prepare_s=t_prep - t_start, device_and_copies_s=t_back - t_prep,
                              host_finish_s=t_end - t_back, total_s=t_end - t_start)
     return results
+
+
+KITTI_STATUS_KINDS = ((1, 0, 'a non-finite box'), (8, 3, 'more rows of one class in one frame than a launch holds'),
+                      (32, 5, 'a workspace slot that is too small'))
+_KITTI_LDS_CELLS = 64 * 64      # frames with more cells than this (rows of all classes) get a workspace slot (section 16)
+_KITTI_MAX_DISTRACTORS = 4
+
+
+def _sorted_by_frame(rows, width):
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, width)
+    frames = rows[:, 0].astype(np.int64)
+    order = np.argsort(frames, kind='stable')
+    return rows[order], frames[order], order
+
+
+def kitti_keep_masks(sequences, classes, max_occlusion=2, max_truncation=0, min_height=25, match_thr=0.5, ignore_thr=0.5,
+                     device=None, videos=None, timing=False):
+    """KITTI's preprocessing (metrics.kitti_preprocess, the specification) of every sequence and class in ONE launch of
+    st_mot_kitti_preprocess: one upload, one launch, one wait and copy back.
+    sequences: a list of (gt_rows (n, 9), pred_rows (m, 8), ignore_boxes (k, 5)) in kitti_preprocess's layouts, rows in
+    any order; classes: a list of (class id, distractor ids).  Returns one (gt_keep (C, n), pred_keep (C, m)) pair of
+    boolean arrays per sequence, over the rows as they were passed.  videos: the sequences' names for error messages.
+    timing: returns (masks, dict) with the stage's device time (HIP events) and the host clock of the call's parts."""
+    t_start = time.perf_counter()
+    if not torch.cuda.is_available():
+        raise RuntimeError('the device backend of the KITTI preprocessing runs on the HIP path only (csrc/mot_eval.hip) '
+                           'and no CUDA (ROCm) device is available; use backend=\'host\'')
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise RuntimeError(f'the device backend of the KITTI preprocessing needs a CUDA (ROCm) device, got {dev}')
+    sequences = list(sequences)
+    videos = list(range(len(sequences))) if videos is None else list(videos)
+    table = np.full((len(classes), 1 + _KITTI_MAX_DISTRACTORS), -1, np.int32)
+    for c, (cid, distractors) in enumerate(classes):
+        distractors = list(distractors)
+        if len(distractors) > _KITTI_MAX_DISTRACTORS or int(cid) < 0 or any(int(d) < 0 for d in distractors):
+            raise ValueError(f'kitti_keep_masks: class {cid} with distractors {distractors}: ids must be >= 0, at most '
+                             f'{_KITTI_MAX_DISTRACTORS} distractors')
+        table[c, 0] = int(cid)
+        table[c, 1:1 + len(distractors)] = [int(d) for d in distractors]
+    C_ = len(classes)
+    if C_ == 0 or not sequences:
+        return ([], {}) if timing else []
+
+    # ---- host tables: the frames of a sequence are the union of its three row kinds' frame numbers
+    parts, orders, frame_no, frame_seq = ([], [], []), [], [], []
+    offs = ([0], [0], [0])
+    totals = [0, 0, 0]
+    for s, seq in enumerate(sequences):
+        srt = [_sorted_by_frame(rows, w) for rows, w in zip(seq, (9, 8, 5))]
+        frames = np.unique(np.concatenate([fr for _, fr, _ in srt]))
+        for k, (rows, fr, _) in enumerate(srt):
+            parts[k].append(rows)
+            offs[k].append(totals[k] + np.searchsorted(fr, frames, 'right'))
+            totals[k] += len(rows)
+        orders.append([o for _, _, o in srt])
+        frame_no.append(frames)
+        frame_seq.append(np.full(len(frames), s, np.int32))
+    frame_no, frame_seq = np.concatenate(frame_no), np.concatenate(frame_seq)
+    F = len(frame_no)
+    if max(totals + [F * C_]) >= 2 ** 31 - 1:
+        raise ValueError(f'kitti_keep_masks: {totals} rows, {F} frames x {C_} classes: the offset tables are 32-bit')
+    host_in = dict(gt_rows=np.concatenate(parts[0]), pred_rows=np.concatenate(parts[1]), ignore_rows=np.concatenate(parts[2]),
+                   class_table=table)
+    for k, name in enumerate(('frame_gt_off', 'frame_pred_off', 'frame_ignore_off')):
+        host_in[name] = np.concatenate([np.atleast_1d(a) for a in offs[k]]).astype(np.int32)
+    G, P = np.diff(host_in['frame_gt_off']).astype(np.int64), np.diff(host_in['frame_pred_off']).astype(np.int64)
+    host_in['frame_ws_off'] = np.concatenate([[0], np.cumsum(np.where(G * P > _KITTI_LDS_CELLS, G * P, 0))]).astype(np.int64)
+    NG, NP_, NI = totals
+
+    # ---- one upload
+    lin = _Layout()
+    for k, v in host_in.items():
+        lin.add(k, v.shape, v.dtype)
+    hbuf = np.zeros(lin.size, np.uint8)
+    for k, v in host_in.items():
+        lin.view(hbuf, k)[...] = v
+    t_prep = time.perf_counter()
+    dbuf = torch.from_numpy(hbuf).to(dev)
+    lout = _Layout()
+    for name, shape, dt in (('status', (8,), np.int32), ('gt_keep', (C_, NG), np.uint8), ('pred_keep', (C_, NP_), np.uint8)):
+        lout.add(name, shape, dt)
+    obuf = torch.empty(lout.size, dtype=torch.uint8, device=dev)       # the stage zeroes what it does not write
+
+    args = _lib.StMotKittiArgs()
+    args.struct_size = C.sizeof(_lib.StMotKittiArgs)
+    args.num_frames, args.num_classes, args.num_gt, args.num_pred, args.num_ignore = F, C_, NG, NP_, NI
+    args.max_frame_objects = int(max(G.max(initial=0), P.max(initial=0)))
+    args.num_ws_cells = int(host_in['frame_ws_off'][-1])
+    args.max_occlusion, args.max_truncation, args.min_height = float(max_occlusion), float(max_truncation), float(min_height)
+    args.match_thr, args.ignore_thr = float(match_thr), float(ignore_thr)
+    for k in host_in:
+        setattr(args, k, C.c_void_p(dbuf.data_ptr() + lin.items[k][0]))
+    for k in lout.items:
+        setattr(args, k, C.c_void_p(obuf.data_ptr() + lout.items[k][0]))
+    nbytes = int(lib.st_mot_kitti_workspace_bytes(C.byref(args)))
+    if nbytes == 0:
+        raise _lib.StError('st_mot_kitti_workspace_bytes: invalid sizes')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    args.ws, args.ws_bytes = C.c_void_p(ws.data_ptr()), nbytes
+    with torch.cuda.device(dev):
+        events = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing else None
+        if timing:
+            events[0].record()
+        LAUNCHES['st_mot_kitti_preprocess'] += 1
+        check(lib.st_mot_kitti_preprocess(C.byref(args), current_stream()), 'st_mot_kitti_preprocess')
+        if timing:
+            events[1].record()
+    host = obuf.cpu().numpy()          # the one wait and the one copy back
+    t_back = time.perf_counter()
+    status = lout.view(host, 'status')
+    if status[0]:
+        for bit, kind, what in KITTI_STATUS_KINDS:
+            if int(status[0]) & bit:
+                f = F - int(status[1 + kind])
+                msg = f'KITTI preprocessing: {what}: video {videos[int(frame_seq[f])]!r}, frame {int(frame_no[f])}'
+                if bit == 8:
+                    msg += (f' (at most {max_frame_objects()} ground-truth rows of a class and its distractors and '
+                            f'{max_frame_objects()} prediction rows of the class per frame)')
+                raise ValueError(msg) if bit in (1, 8) else _lib.StError(msg)
+        raise _lib.StError(f'KITTI preprocessing failed on the device: status {int(status[0])}')
+    gk, pk = lout.view(host, 'gt_keep'), lout.view(host, 'pred_keep')
+    out, g0, p0 = [], 0, 0
+    for s, seq in enumerate(sequences):
+        og, op_, _ = orders[s]
+        a, b = np.zeros((C_, len(og)), bool), np.zeros((C_, len(op_)), bool)
+        a[:, og] = gk[:, g0:g0 + len(og)] != 0
+        b[:, op_] = pk[:, p0:p0 + len(op_)] != 0
+        g0, p0 = g0 + len(og), p0 + len(op_)
+        out.append((a, b))
+    if timing:
+        t_end = time.perf_counter()
+        return out, dict(stages_ms={'st_mot_kitti_preprocess': events[0].elapsed_time(events[1])},
+                         host_prepare_s=t_prep - t_start, device_and_copies_s=t_back - t_prep,
+                         host_finish_s=t_end - t_back, total_s=t_end - t_start)
+    return out
 
 
 class TrackCollector:
