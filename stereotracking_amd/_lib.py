@@ -106,6 +106,13 @@ class StMotKittiArgs(C.Structure):
         [(n, C.c_void_p) for n in ('gt_keep', 'pred_keep', 'status')]
 
 
+class StTrackletArgs(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('struct_size', 'num_rows', 'num_out_rows', 'num_tracks', 'first', 'count',
+                                       'num_groups', 'max_rows')] + \
+        [(n, C.c_void_p) for n in ('rows', 'row_out_off', 'row_gap', 'trk_out_off', 'trk_order', 'trk_len_scale', 'ws')] + \
+        [('ws_bytes', C.c_size_t), ('out_rows', C.c_void_p), ('status', C.c_void_p), ('phase_ticks', C.c_void_p)]
+
+
 class StStreamTick(C.Structure):
     _fields_ = [('struct_size', C.c_int), ('streams', C.c_int), ('chunk', C.c_int), ('num_chunks', C.c_int),
                 ('max_dets', C.c_int), ('det_rows', C.c_int), ('stream_of_slot', C.c_void_p), ('frame_ids', C.c_void_p)]
@@ -252,6 +259,10 @@ _PROTOS = {
     'st_mot_hota_accumulate': (_i, [C.POINTER(StMotArgs), _vp]),
     'st_mot_kitti_workspace_bytes': (_sz, [C.POINTER(StMotKittiArgs)]),
     'st_mot_kitti_preprocess': (_i, [C.POINTER(StMotKittiArgs), _vp]),
+    'st_tracklet_max_rows': (_i, []),
+    'st_tracklet_gsi_workspace_bytes': (_sz, [C.POINTER(StTrackletArgs)]),
+    'st_tracklet_interpolate': (_i, [C.POINTER(StTrackletArgs), _vp]),
+    'st_tracklet_gsi': (_i, [C.POINTER(StTrackletArgs), _vp]),
     'st_box_depth_method': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _i]),
     'st_stream_record_bytes': (_sz, [_i, _i, _i]),
     'st_stream_gather': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp, _vp]),

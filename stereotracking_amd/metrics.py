@@ -387,9 +387,14 @@ class MOTDroneMetrics(GatheredVideoMetric):
     allowed_metrics = ('HOTA', 'CLEAR', 'Identity')
 
     def __init__(self, depth_thr=80, ignore_depth=False, iou_thr=0.5, metric=('HOTA', 'CLEAR', 'Identity'),
-                 backend='host'):
+                 backend='host', postprocess_tracklet_cfg=()):
         _check_backend(backend)       # 'device': all videos in one mot_eval.evaluate_packed call, at evaluate()
         self.backend = backend
+        # mot_drone_metrics.py:95, 110-113: TASK_UTILS entries applied to every video's prediction rows.  The reference
+        # applies them in process() when a video's last frame arrives (:210-219); process() here has no video length,
+        # so they run once per video at evaluation time (postprocessed_pred), after gather(), on the evaluating rank.
+        self.postprocess_tracklet_methods = [self._build_postprocess(c) for c in (postprocess_tracklet_cfg or ())]
+        self._postprocessed = None
         self.depth_thr, self.ignore_depth, self.iou_thr = depth_thr, ignore_depth, iou_thr
         self.metrics = [metric] if isinstance(metric, str) else list(metric)      # mot_drone_metrics.py:83-103
         for m in self.metrics:
@@ -397,6 +402,33 @@ class MOTDroneMetrics(GatheredVideoMetric):
                 raise KeyError(f'metric {m} is not supported.')
         self.pred = defaultdict(list)
         self.gt = defaultdict(list)
+
+    def _build_postprocess(self, cfg):
+        from .registry import TASK_UTILS
+        from . import tracklets  # noqa: F401  (registers InterpolateTracklets)
+        if not isinstance(cfg, dict):
+            return cfg                                    # an instance, used as it is
+        if str(cfg.get('type', '')).split('.')[-1] == 'AppearanceFreeLink':
+            raise NotImplementedError('postprocess_tracklet_cfg: AppearanceFreeLink needs a trained link network and its '
+                                      'checkpoint, which are not available; InterpolateTracklets is supported')
+        cfg = dict(cfg)
+        cfg.setdefault('backend', self.backend)           # an entry without a backend inherits the metric's
+        return TASK_UTILS.build(cfg)
+
+    def postprocessed_pred(self):
+        """video -> prediction rows after the post-processing entries (the collected rows without any): what is scored
+        and written.  Every entry sees all videos in one forward_many call; the result is kept until rows are added, so
+        write_motchallenge and evaluate share one pass."""
+        if not self.postprocess_tracklet_methods:
+            return self.pred
+        videos = sorted(self.pred)
+        key = (id(self.pred), tuple((v, len(self.pred[v])) for v in videos))   # process() appends, gather() replaces
+        if self._postprocessed is None or self._postprocessed[0] != key:
+            rows = [np.asarray(self.pred[v], dtype=np.float64).reshape(-1, 7) for v in videos]
+            for method in self.postprocess_tracklet_methods:
+                rows = method.forward_many(rows)
+            self._postprocessed = (key, dict(zip(videos, rows)))
+        return self._postprocessed[1]
 
     def process(self, video, data_sample, gt_instances=None):
         """data_sample: TrackDataSample with pred_track_instances (+ metainfo frame_id);
@@ -423,7 +455,7 @@ class MOTDroneMetrics(GatheredVideoMetric):
         """pred: frame,id,x,y,w,h,score,-1,-1,-1   gt: frame,id,x,y,w,h,conf,class,visibility (reference :223-253)."""
         os.makedirs(os.path.join(out_dir, 'pred'), exist_ok=True)
         os.makedirs(os.path.join(out_dir, 'gt'), exist_ok=True)
-        for video, rows in self.pred.items():
+        for video, rows in self.postprocessed_pred().items():
             with open(os.path.join(out_dir, 'pred', video + '.txt'), 'wt') as f:
                 for t in rows:
                     f.write('%d,%d,%.3f,%.3f,%.3f,%.3f,%.3f,-1,-1,-1\n' % tuple(t[:7]))
@@ -434,16 +466,21 @@ class MOTDroneMetrics(GatheredVideoMetric):
 
     def _evaluate_local(self):
         videos = sorted(set(self.gt) | set(self.pred))
+        pred = self.postprocessed_pred()
         if self.backend == 'device':
             from . import mot_eval
-            packed = mot_eval.pack_sequences({v: self.gt.get(v, []) for v in videos}, {v: self.pred.get(v, []) for v in videos})
+            packed = mot_eval.pack_sequences({v: self.gt.get(v, []) for v in videos}, {v: pred.get(v, []) for v in videos})
             wanted = ['CLEAR', 'Identity'] + (['HOTA'] if 'HOTA' in self.metrics else [])
             scored = dict(zip(packed['videos'], mot_eval.evaluate_packed(packed, self.iou_thr, wanted)))
             per_video = {v: scored[v]['clear_identity'] for v in videos}
         else:
-            per_video = {v: clear_identity(self.gt.get(v, []), self.pred.get(v, []), self.iou_thr) for v in videos}
+            per_video = {v: clear_identity(self.gt.get(v, []), pred.get(v, []), self.iou_thr) for v in videos}
         hs = None
         if 'HOTA' in self.metrics:
             hs = {v: scored[v]['hota'] for v in per_video} if self.backend == 'device' else \
-                {v: hota(self.gt.get(v, []), self.pred.get(v, [])) for v in per_video}
+                {v: hota(self.gt.get(v, []), pred.get(v, [])) for v in per_video}
         return dict(per_video=per_video, combined=combine_videos(per_video, hs))
+
+
+from .registry import METRICS  # noqa: E402
+METRICS.register_module(name=['MOTDroneMetrics', 'mmtrack.MOTDroneMetrics'], module=MOTDroneMetrics)

@@ -34,6 +34,7 @@ from . import stereo as _stereo  # noqa: F401  (registers StereoCostVolume)
 from . import sgbm as _sgbm  # noqa: F401  (registers StereoSGBM)
 from . import coco_metric as _coco_metric  # noqa: F401  (registers CocoMetric in METRICS)
 from . import kitti_metrics as _kitti_metrics  # noqa: F401  (registers MOTKittiMetrics in METRICS)
+from . import tracklets as _tracklets  # noqa: F401  (registers InterpolateTracklets in TASK_UTILS)
 
 
 def stack_batch(tensors, pad_size_divisor=0, pad_value=0):

@@ -486,13 +486,22 @@ class TrackCollector:
         return out
 
 
-def evaluate_sweep(predictions, gt, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None, backend='device'):
+def evaluate_sweep(predictions, gt, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None, backend='device',
+                   postprocess=None):
     """Scores the B prediction sets of a batched tracker run (a TrackCollector, or a list of B row arrays) against one
     ground-truth row array (shared) or a list of B of them.  Returns B dicts as evaluate_packed does.  A collector's
     rows are scaled back to image space (TrackCollector.prediction_rows), so the ground truth is the image-space one;
     row arrays passed directly are scored as they are.
-    backend='host' scores the same rows with metrics.clear_identity / metrics.hota (the reference of the tests)."""
+    backend='host' scores the same rows with metrics.clear_identity / metrics.hota (the reference of the tests).
+    postprocess: a tracklets.InterpolateTracklets (or a list of them, applied in order) run over the B prediction sets
+    before they are scored, each through one forward_many call on its own backend; 6-column rows (a collector's)
+    get the score 1.0 first."""
     preds = predictions.prediction_rows() if isinstance(predictions, TrackCollector) else list(predictions)
+    if postprocess is not None:
+        preds = [np.asarray(p, dtype=np.float64).reshape(-1, np.shape(p)[-1] if np.size(p) else 7) for p in preds]
+        preds = [np.column_stack([p, np.ones(len(p))]) if p.shape[1] == 6 else p for p in preds]
+        for method in (postprocess if isinstance(postprocess, (list, tuple)) else [postprocess]):
+            preds = method.forward_many(preds)
     gts = list(gt) if isinstance(gt, (list, tuple)) else [gt] * len(preds)
     if len(gts) != len(preds):
         raise ValueError(f'evaluate_sweep: {len(preds)} prediction sets against {len(gts)} ground-truth sets')
