@@ -2,7 +2,9 @@
 kernel against their oracles.  Cost volume and stand-alone soft-argmin / upsample are BIT-EXACT
 (same fmaf order as oracle/st_oracle.c); the fused soft-argmin merges disparity groups in a
 different order, so it is held to 1e-3 (north_star's float tolerance); box depth: exact decisions
-(-1 / NaN / scale clamps), floats within 1e-3."""
+(-1 / NaN / scale clamps), floats within 1e-3 of oracle/depth.py here.  The tight pin of the default
+estimator (1 fp32 ulp of its float64 restatement, on crafted ties, branches and geometries) is
+tests/test_box_depth_default_gpu.py."""
 import ctypes as C
 import math
 
