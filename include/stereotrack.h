@@ -1025,6 +1025,65 @@ int st_tracklet_interpolate(const StTrackletArgs* args, st_stream_t stream);
 int st_tracklet_gsi(const StTrackletArgs* args, st_stream_t stream);
 
 /* ----------------------------------------------------------------------
+ * 18. AppearanceFreeLink (AFLink, StrongSORT) on the device, csrc/aflink.hip.  Replaces the double loop of the
+ *     reference's mmtrack/models/task_modules/track/aflink.py:230-259 (gate, data_transform and one batch-1 forward
+ *     of the link network per pair); the rules are the statements of stereotracking_amd/aflink.py (backend='host',
+ *     DESIGN.md section 18).  The linear assignment and the relabelling stay on the host.
+ *   tables   built by the host: feat (num_rows, 3) fp64 = (frame, c0, c1) of every row, the tracks of all prediction
+ *            sets one after the other, a set's tracks by (first frame, id), a track's rows ascending in frame;
+ *            trk_off (num_tracks + 1) first row of every track; trk_set (num_tracks) the set of every track; set_off
+ *            (num_sets + 1) first track of every set.  An entry that points outside the buffers sets header bit 2.
+ *   header   2 ints, zeroed by st_aflink_gate: [0] the number of candidates, [1] status bits: 1 more candidates than
+ *            `capacity` (the list holds the first `capacity`), 2 a table entry out of range.
+ *   st_aflink_gate       every ordered pair i != j of a set with t_lo <= first_frame(j) - last_frame(i) <= t_hi and
+ *            sqrt(dx * dx + dy * dy) <= spatial_thr (unfused fp64, the corners of i's last and j's first row) is a
+ *            candidate.  A counting pass, an exclusive prefix sum (ws_off, num_tracks + 1 ints) and a filling pass:
+ *            cand (capacity, 3) ints = (set, i, j) with i, j counted inside the set, row-major, no atomics.
+ *   st_aflink_transform  candidates [first, first + count) (those at or past header[0] are skipped) -> ws_x
+ *            (count, 2, 30, 3) fp32: i's last 30 rows (zero rows in front), j's first 30 (zero rows behind), every
+ *            column (v - (max + min) / 2) / ((max - min) / 2 + 1e-5) over all 60 rows in fp64, rounded once.
+ *   st_aflink_score      ws_x -> conf[first ...]: the softmax probability of class 1; logits (optional, NULL: off)
+ *            (capacity, 2) the two fp32 logits.  One workgroup per st_aflink_group_pairs() candidates, activations in
+ *            LDS, layers 2-4 and the fusion conv on v_mfma_f32_32x32x2_f32 (exact fp32).  A candidate's bytes do not
+ *            depend on its neighbours, the range or the launch.
+ *   st_aflink_run        gate, then transform + score over [0, capacity) in rounds of `chunk` candidates (ws_x holds
+ *            chunk x 180 floats).  capacity: any upper bound of the candidate count the host knows (aflink.py takes
+ *            the pairs that pass the temporal rule), at most st_aflink_max_candidates().
+ *   weights  st_aflink_weights_create copies st_aflink_packed_floats() floats (BatchNorm folded to scale and shift by
+ *            the host; the layout is written out at the top of csrc/aflink.hip and in aflink.pack_weights) to the
+ *            device; the library owns that copy until st_aflink_weights_destroy.  These two calls allocate and wait;
+ *            the stage calls are enqueued on `stream`, no host wait, no allocation.  All other buffers are the
+ *            caller's.  A call that returns non-zero has written nothing.
+ * ---------------------------------------------------------------------- */
+typedef struct StAflinkArgs {
+  int struct_size;              /* sizeof(StAflinkArgs) */
+  int num_sets, num_tracks, num_rows;
+  int capacity;                 /* slots of cand / conf / logits */
+  int first, count;             /* st_aflink_transform, st_aflink_score: the candidate range of this call */
+  int chunk;                    /* st_aflink_run: candidates per round */
+  double t_lo, t_hi, spatial_thr;
+  const double* feat;
+  const int* trk_off;
+  const int* trk_set;
+  const int* set_off;
+  int* ws_off;
+  float* ws_x;
+  int* header;
+  int* cand;
+  float* conf;
+  float* logits;
+} StAflinkArgs;
+int st_aflink_group_pairs(void);
+size_t st_aflink_packed_floats(void);
+int st_aflink_max_candidates(void);
+int st_aflink_weights_create(const float* packed_host, size_t num_floats, void** handle);
+int st_aflink_weights_destroy(void* handle);
+int st_aflink_gate(const StAflinkArgs* args, st_stream_t stream);
+int st_aflink_transform(const StAflinkArgs* args, st_stream_t stream);
+int st_aflink_score(const StAflinkArgs* args, const void* weights, st_stream_t stream);
+int st_aflink_run(const StAflinkArgs* args, const void* weights, st_stream_t stream);
+
+/* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call
  * (mmtrack/datasets/transforms/loading_disparity.py:74-75 uint16 disparity, :213-215 uint16 depth; mmcv's

@@ -113,6 +113,14 @@ class StTrackletArgs(C.Structure):
         [('ws_bytes', C.c_size_t), ('out_rows', C.c_void_p), ('status', C.c_void_p), ('phase_ticks', C.c_void_p)]
 
 
+class StAflinkArgs(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('struct_size', 'num_sets', 'num_tracks', 'num_rows', 'capacity', 'first', 'count',
+                                       'chunk')] + \
+        [(n, C.c_double) for n in ('t_lo', 't_hi', 'spatial_thr')] + \
+        [(n, C.c_void_p) for n in ('feat', 'trk_off', 'trk_set', 'set_off', 'ws_off', 'ws_x', 'header', 'cand', 'conf',
+                                   'logits')]
+
+
 class StStreamTick(C.Structure):
     _fields_ = [('struct_size', C.c_int), ('streams', C.c_int), ('chunk', C.c_int), ('num_chunks', C.c_int),
                 ('max_dets', C.c_int), ('det_rows', C.c_int), ('stream_of_slot', C.c_void_p), ('frame_ids', C.c_void_p)]
@@ -263,6 +271,15 @@ _PROTOS = {
     'st_tracklet_gsi_workspace_bytes': (_sz, [C.POINTER(StTrackletArgs)]),
     'st_tracklet_interpolate': (_i, [C.POINTER(StTrackletArgs), _vp]),
     'st_tracklet_gsi': (_i, [C.POINTER(StTrackletArgs), _vp]),
+    'st_aflink_group_pairs': (_i, []),
+    'st_aflink_packed_floats': (_sz, []),
+    'st_aflink_max_candidates': (_i, []),
+    'st_aflink_weights_create': (_i, [_vp, _sz, C.POINTER(_vp)]),
+    'st_aflink_weights_destroy': (_i, [_vp]),
+    'st_aflink_gate': (_i, [C.POINTER(StAflinkArgs), _vp]),
+    'st_aflink_transform': (_i, [C.POINTER(StAflinkArgs), _vp]),
+    'st_aflink_score': (_i, [C.POINTER(StAflinkArgs), _vp, _vp]),
+    'st_aflink_run': (_i, [C.POINTER(StAflinkArgs), _vp, _vp]),
     'st_box_depth_method': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _i]),
     'st_stream_record_bytes': (_sz, [_i, _i, _i]),
     'st_stream_gather': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -493,9 +493,9 @@ def evaluate_sweep(predictions, gt, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Iden
     rows are scaled back to image space (TrackCollector.prediction_rows), so the ground truth is the image-space one;
     row arrays passed directly are scored as they are.
     backend='host' scores the same rows with metrics.clear_identity / metrics.hota (the reference of the tests).
-    postprocess: a tracklets.InterpolateTracklets (or a list of them, applied in order) run over the B prediction sets
-    before they are scored, each through one forward_many call on its own backend; 6-column rows (a collector's)
-    get the score 1.0 first."""
+    postprocess: any entry with forward_many(list of row arrays) -> list - a tracklets.InterpolateTracklets, an
+    aflink.AppearanceFreeLink - or a list of them, applied in order over the B prediction sets before they are scored,
+    each through one forward_many call on its own backend; 6-column rows (a collector's) get the score 1.0 first."""
     preds = predictions.prediction_rows() if isinstance(predictions, TrackCollector) else list(predictions)
     if postprocess is not None:
         preds = [np.asarray(p, dtype=np.float64).reshape(-1, np.shape(p)[-1] if np.size(p) else 7) for p in preds]
