@@ -840,7 +840,7 @@ bool pwr_chain_applicable(const StConvDesc& d, const StConvDesc& c);
 bool dc_conv_applicable(const StConvDesc& d);          // direct_conv.hip (tile variant 42)
 int dc_conv_launch(const StConvDesc& d, hipStream_t stream);
 bool wino_conv_applicable(const StConvDesc& d);        // wino_conv.hip (tile variant 43)
-int wino_conv_launch(const StConvDesc& d, hipStream_t stream, bool narrow);
+int wino_conv_launch(const StConvDesc& d, hipStream_t stream, bool narrow, bool parent_sched);
 int wino_persist_launch(const StConvDesc& d, hipStream_t stream);   // wino_conv.hip (tile variant 57)
 
 int conv2d_launch(const StConvDesc& d, hipStream_t stream, int force_variant, int* picked_variant) {
@@ -859,9 +859,13 @@ int conv2d_launch(const StConvDesc& d, hipStream_t stream, int force_variant, in
   }
   if (force_variant == 43 || force_variant == 44) {   // Winograd F(2x2,3x3) kernel (44: 32-cout workgroups)
     if (picked_variant) *picked_variant = force_variant;
-    return wino_conv_launch(d, stream, force_variant == 44);
+    return wino_conv_launch(d, stream, force_variant == 44, false);
   }
 #ifdef ST_ABLATION
+  if (force_variant == 58 || force_variant == 59) {   // tools build: 43 / 44 on the K-loop schedule before the weight ring
+    if (picked_variant) *picked_variant = force_variant;
+    return wino_conv_launch(d, stream, force_variant == 59, true);
+  }
   if (force_variant == 57) {   // tools build: persistent Winograd kernel (bit-identical to 43, not faster: wino_conv.hip)
     if (picked_variant) *picked_variant = 57;
     return wino_persist_launch(d, stream);

@@ -13,12 +13,16 @@
 // U_xi[co][ci].  A workgroup = 4 waves = the 4 rows `a` of the transform; it owns 32 tiles (8 x 4 tiles = 16 x 8 output
 // pixels) x 64 couts, i.e. per wave 4 (b) x 2 (cout blocks of 32) accumulator tiles of 32x32.
 //   * raw input window (18 x 10 pixels x 32 cin per K-chunk, 23 KB) -> LDS by LDS-DMA with hardware zero fill (= the
-//     conv padding and the ragged edge), double buffered, source-side XOR swizzle (2-way conflicts at most);
+//     conv padding and the ragged edge), double buffered, source-side XOR swizzle (2-way conflicts at most); the next
+//     chunk's window is requested behind the chunk's first weight load and first waited for 16 MFMAs later;
 //   * the input transform never touches memory: a lane (tile, 4 channels) reads its 2 x 4 patch pixels with 8
 //     ds_read_b128, forms its wave's row of B^T d (4 adds) and the 4 values V[a][0..3] (4 adds) in registers - those ARE
 //     the A operands of the next 4 x 2 x 4 MFMAs;
 //   * the transformed weights are pre-packed on the host in FRAGMENT ORDER, so every B operand is one fully coalesced
-//     1 KB wave load straight from L2 into VGPRs (1 MB per layer, shared by every workgroup), prefetched one step ahead;
+//     1 KB wave load straight from L2 into VGPRs (1 MB per layer, shared by every workgroup), through a ring of four
+//     named register quads: a load is issued 12 MFMAs before the wait that covers it (the K loop below.  Until the ring
+//     this line read "prefetched one step ahead", which the source said and the binary did not do: the compiler kept
+//     ONE register set and waited for every load 3-4 MFMAs after its issue, and for the next window at once);
 //   * output transform: each wave reduces its own row over b in registers (M -> 2 values), the 4 rows meet through
 //     LDS (64 KB, reusing the window buffers), then bias + SiLU (+ residual) and coalesced NHWC stores.
 #include <algorithm>
@@ -26,6 +30,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "st_common.h"
@@ -66,7 +71,91 @@ struct WinoArgs {
 // (23x40, 46x80) whose grid otherwise fills less than one round of the chip.
 // KTAIL: Cin % 32 != 0 (the 48-level aggregation convs): the last K-chunk runs only the channel groups that exist
 // (g_last of 4) instead of multiplying zero-padded channels - a quarter of the layer's MFMAs at Cin = 48.
-template <int CBN, int LCBN, bool RES, bool KTAIL>
+// ---- the weight ring of wino_conv3x3_body: four slots of one 16-byte fragment per lane, in sixteen NAMED registers
+// just above the register budget the ring kernels give the compiler (amdgpu_num_vgpr: 240 for the 64-cout instances,
+// ring v[240:255]; 152 for the 32-cout ones, ring v[152:167] - totals 256 and 168, two and three workgroups per CU as
+// before).  Named, not allocated: as values of the register allocator the ring was merged into one set, or copied at
+// the loop's back edge WHILE ITS LOADS WERE IN FLIGHT; in accumulation registers it halves the compiler's own budget.
+// The compiler never touches a register above its budget (they are RESERVED - which is what the clobber lists are
+// warned about; the clobbers make the kernel descriptor allocate them).  On gfx90a and later amdgpu_num_vgpr counts
+// the unified file in halves: the attribute's value is budget / 2, and a value whose double exceeds what the launch
+// bounds allow is silently ignored - tools/wino_sched_report.py prints the highest register the compiler touches.
+// Loads, waits and MFMAs of the ring are volatile asm statements: they keep their source order, which IS the
+// schedule.  k and n are constants once the slot loop is unrolled.
+constexpr int WN_VGPR_WIDE = 240, WN_VGPR_NARROW = 152;   // the compiler's budget; the ring follows it
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+#define WN_RING_LOAD(R0, R1, R2, R3)                                                                              \
+  asm volatile("buffer_load_dwordx4 v[" #R0 ":" #R3 "], %0, %1, %2 offen" :: "v"(voff), "s"(rsrc), "s"(soff)      \
+               : "v" #R0, "v" #R1, "v" #R2, "v" #R3)
+template <int CBN>
+__device__ __forceinline__ void wn_ring_load(int k, unsigned voff, __amdgpu_buffer_rsrc_t rsrc, int soff) {
+  if constexpr (CBN == 2) {
+    static_assert(WN_VGPR_WIDE == 240, "the register names below are the budget + 0 .. 15");
+    switch (k) {
+      case 0: WN_RING_LOAD(240, 241, 242, 243); break;
+      case 1: WN_RING_LOAD(244, 245, 246, 247); break;
+      case 2: WN_RING_LOAD(248, 249, 250, 251); break;
+      default: WN_RING_LOAD(252, 253, 254, 255); break;
+    }
+  } else {
+    static_assert(WN_VGPR_NARROW == 152, "the register names below are the budget + 0 .. 15");
+    switch (k) {
+      case 0: WN_RING_LOAD(152, 153, 154, 155); break;
+      case 1: WN_RING_LOAD(156, 157, 158, 159); break;
+      case 2: WN_RING_LOAD(160, 161, 162, 163); break;
+      default: WN_RING_LOAD(164, 165, 166, 167); break;
+    }
+  }
+}
+#undef WN_RING_LOAD
+// acc += v[s] (x) slot k, s = 0..3: the four MFMAs of a slot, in the order every schedule of this body keeps.  (v comes
+// from wn_*_mfma, which end on the two wait states a VALU result needs before an MFMA reads it; the s_nop covers a copy
+// the compiler may have put in between.  An accumulate chain needs no states between its MFMAs.)
+#define WN_RING_MFMA4(B0, B1, B2, B3)                                                                                \
+  asm volatile("s_nop 1\n\tv_mfma_f32_32x32x2_f32 %0, %1, v" #B0 ", %0\n\tv_mfma_f32_32x32x2_f32 %0, %2, v" #B1      \
+               ", %0\n\tv_mfma_f32_32x32x2_f32 %0, %3, v" #B2 ", %0\n\tv_mfma_f32_32x32x2_f32 %0, %4, v" #B3 ", %0"  \
+               : "+v"(acc) : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]))
+template <int CBN>
+__device__ __forceinline__ void wn_ring_mfma(int k, f32x16& acc, f32x4 v) {
+  if constexpr (CBN == 2) {
+    switch (k) {
+      case 0: WN_RING_MFMA4(240, 241, 242, 243); break;
+      case 1: WN_RING_MFMA4(244, 245, 246, 247); break;
+      case 2: WN_RING_MFMA4(248, 249, 250, 251); break;
+      default: WN_RING_MFMA4(252, 253, 254, 255); break;
+    }
+  } else {
+    switch (k) {
+      case 0: WN_RING_MFMA4(152, 153, 154, 155); break;
+      case 1: WN_RING_MFMA4(156, 157, 158, 159); break;
+      case 2: WN_RING_MFMA4(160, 161, 162, 163); break;
+      default: WN_RING_MFMA4(164, 165, 166, 167); break;
+    }
+  }
+}
+#undef WN_RING_MFMA4
+#pragma clang diagnostic pop
+__device__ __forceinline__ void wn_vmwait(int n) {
+  switch (n) {
+    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
+    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
+    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;   // (waits for everything: never too weak)
+  }
+}
+#endif
+
+// RING: the K loop's schedule.  true = the hand-scheduled weight ring below (the product); false = the schedule the
+// compiler makes of the plain loop (tools build only: the yardstick of profiles/wino_ring_ab.txt).
+template <int CBN, int LCBN, bool RES, bool KTAIL, bool RING>
 __device__ __forceinline__ void wino_conv3x3_body(const WinoArgs& p, int b_) {
   constexpr int WN_CB = 32 * CBN;                       // couts per workgroup
   constexpr int WN_FRAG_FLOATS = LCBN * 64 * 4;         // one (kc, g, b) step in memory: LCBN cout blocks x 64 lanes x 4
@@ -137,14 +226,6 @@ __device__ __forceinline__ void wino_conv3x3_body(const WinoArgs& p, int b_) {
   constexpr int SPLIT = LCBN / CBN;   // workgroups sharing one layout group
   const unsigned wbase = (unsigned)(((((cb / SPLIT) * 4 + a) * p.nkc) * 16) * WN_FRAG_FLOATS + (cb % SPLIT) * CBN * 256 +
                                     lane * 4) * 4u;
-  const int last_step = p.nkc * 16 - 1;
-  auto load_frag = [&](int step, f32x4 (&f)[CBN]) {   // step = (kc * 4 + g) * 4 + b; the prefetch past the last step
-    // the step displacement is wave-uniform: it rides in the scalar offset, no vector add per load
-    const int soff = (step < last_step ? step : last_step) * (WN_FRAG_FLOATS * 4);
-#pragma unroll
-    for (int nb = 0; nb < CBN; ++nb)
-      f[nb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wbase, soff + 1024 * nb, 0));
-  };
 
   f32x16 acc[4][CBN];
 #pragma unroll
@@ -154,46 +235,163 @@ __device__ __forceinline__ void wino_conv3x3_body(const WinoArgs& p, int b_) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[b][nb][r] = 0.f;
 
-  dma_window(0, 0);
-  f32x4 fe[CBN], fo[CBN];   // weight fragments of the even / odd steps (16 steps per chunk: static assignment)
-  load_frag(0, fe);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kc = 0; kc < p.nkc; ++kc) {
-    const int buf = kc & 1;
-    if (kc + 1 < p.nkc) dma_window(kc + 1, buf ^ 1);   // lands during this chunk's 128 MFMAs
-    const float* win = smem + buf * WN_WIN_FLOATS;
-    const int gn = (KTAIL && kc == p.nkc - 1) ? p.g_last : 4;   // wave-uniform
+  if constexpr (RING) {
+    // ---- K loop on a weight RING.  A SLOT is one cout block of one step: one 1 KB load, four MFMAs.  Slot c of a chunk
+    // lives in ring register c % NR (wn_ring_load above); its load is issued in front of the MFMAs of slot c - AHEAD, so
+    // AHEAD * 4 = 12 MFMAs (768 matrix cycles) run between the issue of a load and the wait that covers it.  Left to the
+    // compiler the ring does not survive (it merges the registers, sinks each load behind the last reader of the old
+    // value and waits for it three MFMAs later: DESIGN.md 5), so loads, window DMA, waits and MFMAs are volatile asm
+    // statements in source order, and the compiler counts none of these loads: every wait is counted here.
+    // vmcnt retires in order: the wait of slot c is vmcnt(loads younger than c's), and the window DMA of the next chunk,
+    // issued at slot 0 behind the load of slot AHEAD, is younger than the loads of slots 0 .. AHEAD only - it is first
+    // forced by the wait of slot AHEAD + 1, 16 MFMAs after its issue.
+    constexpr int AHEAD = 3, NR = AHEAD + 1;
+    constexpr int SL = 16 * CBN, GL = 4 * CBN;          // slots per full chunk, per channel group of 8
+    constexpr int FRAG_BYTES = WN_FRAG_FLOATS * 4;
+    constexpr int NPW_FULL = WN_PIECES - 4 * (NPW - 1);   // waves 0 .. NPW_FULL-1 issue NPW pieces, the others NPW - 1
+    static_assert(GL % NR == 0 && SL % NR == 0, "ring indices are static only if a group is a whole number of ring turns");
+    static_assert(GL > AHEAD, "the first AHEAD loads must exist in every layer (g_last >= 1)");
+    static_assert(SL > AHEAD + 1, "the window DMA must be retired by a slot wait inside its chunk");
+    static_assert(NPW_FULL >= 1 && NPW_FULL <= 4, "every wave issues NPW or NPW - 1 window pieces");
+    static_assert(AHEAD + NPW <= 9, "wn_vmwait covers vmcnt(0 .. 9)");
+    (void)dma_window;                                     // (the compiler-counted form: the other schedule's)
+    const int au = __builtin_amdgcn_readfirstlane(a);     // the wave's row as a scalar: uniform branches, SGPR operands
+    const int nd_wave = au < NPW_FULL ? NPW : NPW - 1;    // window pieces this wave issues per chunk
+    const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane(
+        (int)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) float*)smem));
+    auto dma_window_asm = [&](int kc, int buf) {
+      const bool last = kc == p.nkc - 1;
+      const unsigned soff = (unsigned)kc * 128u;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      if (KTAIL && g >= gn) continue;
-      // raw patch -> V[a][0..3] for this lane's 4 channels (8g + 4h .. + 3)
-      f32x4 d[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        d[k] = *reinterpret_cast<const f32x4*>(win + qoff[k] + (((2 * g + h) ^ qsw[k]) << 2));
-      f32x4 P[4], V[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) P[c] = wn_addsgn(d[c], sgn, d[4 + c]);
-      V[0] = wn_sub_mfma(P[0], P[2]);
-      V[1] = wn_add_mfma(P[1], P[2]);
-      V[2] = wn_sub_mfma(P[2], P[1]);
-      V[3] = wn_sub_mfma(P[1], P[3]);
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int step = (kc * 4 + g) * 4 + b;
-        if (b & 1) load_frag(step + 1, fe); else load_frag(step + 1, fo);   // next step's weights (L2, 1 KB each)
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int nb = 0; nb < CBN; ++nb)
-            acc[b][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[b][s], (b & 1) ? fo[nb][s] : fe[nb][s], acc[b][nb],
-                                                              0, 0, 0);
+      for (int k = 0; k < NPW; ++k) {
+        const unsigned off = (last && !((tail_ok >> k) & 1u)) ? 0x80000000u : poff[k];
+        const unsigned dst = lds0 + (unsigned)(buf * WN_WIN_FLOATS + (au + 4 * k) * 256) * 4u;
+        if (k < NPW - 1 || au < NPW_FULL) {   // wave-uniform
+          unsigned keep;
+          asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\t"
+                       "s_mov_b32 m0, %0"
+                       : "=&s"(keep) : "v"(off), "s"(dst), "s"(irsrc), "s"(soff) : "memory");
+        }
       }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of chunk kc + 1 (and the prefetch) landed
+    };
+    // The patch addresses of qoff[] / qsw[] in six registers instead of sixteen (the 32-cout instances have 152 for the
+    // compiler): patch pixel (row r, column c) is window pixel q = qb + c with qb even, so columns (0, 1) and (2, 3)
+    // share a swizzle term, and (2g + h) ^ sw = 2g ^ (h ^ sw): two row bases + four terms, 8g folded at compile time.
+    const int qb0 = (2 * tyi + r0) * WN_WW + 2 * txi, qb1 = (2 * tyi + r1) * WN_WW + 2 * txi;
+    const int hs00 = (h ^ ((qb0 >> 1) & 7)) << 2, hs01 = (h ^ (((qb0 >> 1) + 1) & 7)) << 2;
+    const int hs10 = (h ^ ((qb1 >> 1) & 7)) << 2, hs11 = (h ^ (((qb1 >> 1) + 1) & 7)) << 2;
+    // byte displacement of slot c, counted from its chunk's first step (c >= SL: a slot of the next chunk)
+    auto slot_byte = [](int c) { return (c / CBN) * FRAG_BYTES + (c % CBN) * 1024; };
+
+    dma_window_asm(0, 0);
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k) wn_ring_load<CBN>(k, wbase, wrsrc, slot_byte(k));
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(AHEAD) : "memory");   // the window landed; the ring stays in flight
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+
+    // One K-chunk.  The last chunk is a copy of its own (lastc is a compile-time tag): no window DMA, and the only place
+    // where the stream ends - the steady-state chunks carry no branch but the one between the two DMA counts.
+    auto chunk = [&](int kc, auto last_tag) {
+      constexpr bool lastc = decltype(last_tag)::value;
+      const int buf = kc & 1;
+      const int nd = lastc ? 0 : nd_wave;                    // DMA loads this wave issues in this chunk
+      const int gn = (KTAIL && lastc) ? p.g_last : 4;        // wave-uniform
+      const int sbase = kc * (16 * FRAG_BYTES);
+      const float* win = smem + buf * WN_WIN_FLOATS;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        if (KTAIL && g >= gn) continue;
+        const bool more = g + 1 < gn || !lastc;              // the slots behind this group exist (wave-uniform)
+        // raw patch -> V[a][0..3] for this lane's 4 channels (8g + 4h .. + 3)
+        f32x4 d[8];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          d[c] = *reinterpret_cast<const f32x4*>(win + qb0 * 32 + 32 * c + ((8 * g) ^ (c < 2 ? hs00 : hs01)));
+          d[4 + c] = *reinterpret_cast<const f32x4*>(win + qb1 * 32 + 32 * c + ((8 * g) ^ (c < 2 ? hs10 : hs11)));
+        }
+        f32x4 P[4], V[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) P[c] = wn_addsgn(d[c], sgn, d[4 + c]);
+        V[0] = wn_sub_mfma(P[0], P[2]);
+        V[1] = wn_add_mfma(P[1], P[2]);
+        V[2] = wn_sub_mfma(P[2], P[1]);
+        V[3] = wn_sub_mfma(P[1], P[3]);
+#pragma unroll
+        for (int r = 0; r < GL; ++r) {
+          const int c = g * GL + r, b = r / CBN, nb = r % CBN;
+          const int w_in = GL - 1 - r < AHEAD ? GL - 1 - r : AHEAD;   // younger loads that belong to this group
+          const bool cross = r + AHEAD >= GL;                         // slot c + AHEAD lies behind this group
+          if (!cross || more) wn_ring_load<CBN>((c + AHEAD) % NR,wbase, wrsrc, sbase + slot_byte(c + AHEAD));
+          if (c == 0 && !lastc) dma_window_asm(kc + 1, buf ^ 1);      // (nd > 0 implies `more`: not the last chunk)
+          if (cross && !more) wn_vmwait(w_in);                        // the stream ends with this group: count down
+          else if (c <= AHEAD && nd == NPW) wn_vmwait(AHEAD + NPW);
+          else if (c <= AHEAD && nd == NPW - 1) wn_vmwait(AHEAD + NPW - 1);
+          else wn_vmwait(AHEAD);
+          wn_ring_mfma<CBN>(c % NR, acc[b][nb], V[b]);
+        }
+      }
+      // This wave's pieces of the next window landed at the wait of slot AHEAD + 1; the barrier publishes them and frees
+      // this chunk's buffer.  No vmcnt here: the AHEAD loads of the next chunk stay in flight across the barrier.
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+    };
+    for (int kc = 0; kc + 1 < p.nkc; ++kc) chunk(kc, std::false_type{});
+    chunk(p.nkc - 1, std::true_type{});
+    // the stream ended on vmcnt(0): nothing of the ring is in flight behind the loop
+  } else {
+    // ---- the K loop as the compiler schedules it (fe / fo end up in ONE register set, every load waited on 3-4 MFMAs
+    // after its issue, the next window waited on in front of the chunk's first MFMA)
+    const int last_step = p.nkc * 16 - 1;
+    auto load_frag = [&](int step, f32x4 (&f)[CBN]) {   // step = (kc * 4 + g) * 4 + b; past the last step: a clamped re-load
+      // the step displacement is wave-uniform: it rides in the scalar offset, no vector add per load
+      const int soff = (step < last_step ? step : last_step) * (WN_FRAG_FLOATS * 4);
+#pragma unroll
+      for (int nb = 0; nb < CBN; ++nb)
+        f[nb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wbase, soff + 1024 * nb, 0));
+    };
+    dma_window(0, 0);
+    f32x4 fe[CBN], fo[CBN];   // weight fragments of the even / odd steps (16 steps per chunk: static assignment)
+    load_frag(0, fe);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+
+    for (int kc = 0; kc < p.nkc; ++kc) {
+      const int buf = kc & 1;
+      if (kc + 1 < p.nkc) dma_window(kc + 1, buf ^ 1);
+      const float* win = smem + buf * WN_WIN_FLOATS;
+      const int gn = (KTAIL && kc == p.nkc - 1) ? p.g_last : 4;   // wave-uniform
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        if (KTAIL && g >= gn) continue;
+        // raw patch -> V[a][0..3] for this lane's 4 channels (8g + 4h .. + 3)
+        f32x4 d[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          d[k] = *reinterpret_cast<const f32x4*>(win + qoff[k] + (((2 * g + h) ^ qsw[k]) << 2));
+        f32x4 P[4], V[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) P[c] = wn_addsgn(d[c], sgn, d[4 + c]);
+        V[0] = wn_sub_mfma(P[0], P[2]);
+        V[1] = wn_add_mfma(P[1], P[2]);
+        V[2] = wn_sub_mfma(P[2], P[1]);
+        V[3] = wn_sub_mfma(P[1], P[3]);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int step = (kc * 4 + g) * 4 + b;
+          if (b & 1) load_frag(step + 1, fe); else load_frag(step + 1, fo);   // next step's weights (L2, 1 KB each)
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int nb = 0; nb < CBN; ++nb)
+              acc[b][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(V[b][s], (b & 1) ? fo[nb][s] : fe[nb][s], acc[b][nb],
+                                                                0, 0, 0);
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of chunk kc + 1 (and the prefetch) landed
+      __syncthreads();
+    }
   }
 
   // ---- output transform.  Row reduction over b in registers: R[0] = M0 + M1 + M2, R[1] = M1 - M2 - M3
@@ -264,7 +462,8 @@ __device__ __forceinline__ void wino_conv3x3_body(const WinoArgs& p, int b_) {
     }
   }
 #else
-  (void)smem; (void)i; (void)h; (void)tyi; (void)txi; (void)cb; (void)n; (void)wy0; (void)wx0;
+  (void)smem; (void)i; (void)h; (void)tyi; (void)txi; (void)cb; (void)n; (void)wy0; (void)wx0; (void)a;
+  (void)WN_CB; (void)WN_FRAG_FLOATS;
 #endif
 }
 
@@ -304,12 +503,30 @@ static unsigned wn_grid(long long blocks, unsigned ncb, unsigned order, unsigned
   return (unsigned)blocks;
 }
 
+// The ring kernels: one template per register budget (the attribute takes a literal).  _w = 64-cout workgroups, _n = 32.
+template <bool RES, bool KTAIL>
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(120))) void wino_conv3x3_kernel_w(const WinoArgs p) {
+  static_assert(WN_VGPR_WIDE == 2 * 120, "amdgpu_num_vgpr above");
+  unsigned b;
+  if (!wn_block_of(blockIdx.x, p.order, p.per_xcd, (unsigned)p.ncb, p.nblocks, b)) return;   // uniform
+  wino_conv3x3_body<2, 2, RES, KTAIL, true>(p, (int)b);
+}
+template <int LCBN, bool RES, bool KTAIL>
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(76))) void wino_conv3x3_kernel_n(const WinoArgs p) {
+  static_assert(WN_VGPR_NARROW == 2 * 76, "amdgpu_num_vgpr above");
+  unsigned b;
+  if (!wn_block_of(blockIdx.x, p.order, p.per_xcd, (unsigned)p.ncb, p.nblocks, b)) return;   // uniform
+  wino_conv3x3_body<1, LCBN, RES, KTAIL, true>(p, (int)b);
+}
+#ifdef ST_ABLATION
+// the schedule before the ring, as it was built (no register budget): tile variants 58 / 59, ST_WINO_SCHED=parent
 template <int CBN, int LCBN, bool RES, bool KTAIL>
 __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(const WinoArgs p) {
   unsigned b;
   if (!wn_block_of(blockIdx.x, p.order, p.per_xcd, (unsigned)p.ncb, p.nblocks, b)) return;   // uniform
-  wino_conv3x3_body<CBN, LCBN, RES, KTAIL>(p, (int)b);
+  wino_conv3x3_body<CBN, LCBN, RES, KTAIL, false>(p, (int)b);
 }
+#endif
 
 // GROUPED launch: up to WN_GROUP_MAX independent layers of the same instance (same cout blocking, no residual) share
 // ONE grid - an array of problem descriptors in the kernel arguments, a workgroup finds its problem by the prefix of
@@ -325,8 +542,8 @@ struct WinoGroupArgs {
   int n;
 };
 
-template <int CBN, int LCBN>
-__global__ __launch_bounds__(256, 2) void wino_conv3x3_group_kernel(const WinoGroupArgs g) {
+template <bool RING>
+__device__ __forceinline__ void wino_conv3x3_group_body(const WinoGroupArgs& g) {
   const unsigned bid = blockIdx.x;
   int k = 0;
 #pragma unroll
@@ -334,8 +551,17 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_group_kernel(const WinoGr
   // every problem owns a grid range of its own that starts at a multiple of 8: the local id keeps the block's XCD
   unsigned b;
   if (!wn_block_of(bid - g.first[k], g.p[k].order, g.p[k].per_xcd, (unsigned)g.p[k].ncb, g.p[k].nblocks, b)) return;
-  wino_conv3x3_body<CBN, LCBN, false, false>(g.p[k], (int)b);
+  wino_conv3x3_body<2, 2, false, false, RING>(g.p[k], (int)b);
 }
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(120))) void wino_conv3x3_group_kernel(
+    const WinoGroupArgs g) {
+  wino_conv3x3_group_body<true>(g);
+}
+#ifdef ST_ABLATION
+__global__ __launch_bounds__(256, 2) void wino_conv3x3_group_kernel_parent(const WinoGroupArgs g) {
+  wino_conv3x3_group_body<false>(g);
+}
+#endif
 
 
 #ifdef ST_ABLATION
@@ -344,6 +570,10 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_group_kernel(const WinoGr
 // 1.035 x on the path's eight layer shapes.  The per-workgroup prologue is therefore not what holds these launches at an
 // MFMA-pipe busy of 0.44-0.53; what the tail kernel removed and this form keeps is the transformed-weight stream (1 KB per
 // 4 MFMAs and wave from L2, a wait per step).  Kept as the yardstick of that statement, not shipped.
+// (Measured since: with that stream on a real ring - every load 12 MFMAs ahead, the window 16, wino_conv3x3_body<.., RING>
+// - the per-block form gains 1.02-1.05 x on these shapes at 64 couts and 1.07-1.13 x at 32 (profiles/wino_ring_ab.txt).
+// The ring this form tried in round 6 left registers and waits to the compiler, and its binary was not read: the "no"
+// of profiles/r06_wino_persist_ab.txt stands for that build, not for the latency.)
 // What the counters said about every non-head Winograd launch (MFMA-pipe busy 0.44-0.53, profiles/r06_mfma_busy.txt): a
 // workgroup runs two to four K-chunks between a prologue (index set-up, the first window and weight fetch, exposed) and an
 // epilogue, and dies.  Here two workgroups per CU LOOP over the tile blocks: the NEXT block's first window is requested by
@@ -647,13 +877,36 @@ bool wino_conv_applicable(const StConvDesc& d) {
   return true;
 }
 
-template <int CBN, int LCBN, bool RES, bool KTAIL = false>
+// Which K-loop schedule a launch runs.  The product has the weight ring only; the tools build also carries the schedule
+// before it (tile variants 58 / 59 = 43 / 44 on that schedule; ST_WINO_SCHED=parent switches EVERY Winograd launch,
+// the grouped ones and the detector plan's included, for A/B runs of the whole path).
+static bool wn_ring() {
+#ifdef ST_ABLATION
+  if (const char* e = getenv("ST_WINO_SCHED")) return strcmp(e, "parent") != 0;
+#endif
+  return true;
+}
+
+template <bool RING, int CBN, int LCBN, bool RES, bool KTAIL = false>
 static int wino_launch_instance(const WinoArgs& a, unsigned blocks, hipStream_t stream) {
   constexpr int lds = wn_lds_floats(CBN) * (int)sizeof(float);
   static int lds_set = 0;
-  auto kern = wino_conv3x3_kernel<CBN, LCBN, RES, KTAIL>;
-  ST_ENSURE_DYNAMIC_LDS(kern, lds, lds_set);
-  hipLaunchKernelGGL(kern, dim3(a.grid), dim3(256), lds, stream, a);
+  if constexpr (!RING) {
+#ifdef ST_ABLATION
+    auto kern = wino_conv3x3_kernel<CBN, LCBN, RES, KTAIL>;
+    ST_ENSURE_DYNAMIC_LDS(kern, lds, lds_set);
+    hipLaunchKernelGGL(kern, dim3(a.grid), dim3(256), lds, stream, a);
+#endif
+  } else if constexpr (CBN == 2) {
+    static_assert(CBN != 2 || LCBN == 2, "64-cout workgroups run on the 64-cout layout");
+    auto kern = wino_conv3x3_kernel_w<RES, KTAIL>;
+    ST_ENSURE_DYNAMIC_LDS(kern, lds, lds_set);
+    hipLaunchKernelGGL(kern, dim3(a.grid), dim3(256), lds, stream, a);
+  } else {
+    auto kern = wino_conv3x3_kernel_n<LCBN, RES, KTAIL>;
+    ST_ENSURE_DYNAMIC_LDS(kern, lds, lds_set);
+    hipLaunchKernelGGL(kern, dim3(a.grid), dim3(256), lds, stream, a);
+  }
   return ST_OK;
 }
 
@@ -689,22 +942,33 @@ static int wino_fill_args(const StConvDesc& d, bool narrow, WinoArgs& a, long lo
 }
 
 // narrow = true: 32-cout workgroups on a 64-cout layout (tile variant 44; only where the layout has 2 blocks)
-int wino_conv_launch(const StConvDesc& d, hipStream_t stream, bool narrow) {
-  WinoArgs a;
-  long long blocks = 0;
-  ST_CHECK(wino_fill_args(d, narrow, a, &blocks));
+template <bool RING>
+static int wino_conv_dispatch(const StConvDesc& d, const WinoArgs& a, unsigned blocks, bool narrow, hipStream_t stream) {
   const int lcbn = wino_cbn(d.Cout);
   const int cbn = narrow ? 1 : lcbn;
   const bool ktail = a.g_last < 4;
+  if (ktail && cbn == 2 && !d.res_dev) return wino_launch_instance<RING, 2, 2, false, true>(a, blocks, stream);
+  if (ktail && cbn == 1 && lcbn == 1 && !d.res_dev) return wino_launch_instance<RING, 1, 1, false, true>(a, blocks, stream);
+  if (cbn == 2) return d.res_dev ? wino_launch_instance<RING, 2, 2, true>(a, blocks, stream)
+                                 : wino_launch_instance<RING, 2, 2, false>(a, blocks, stream);
+  if (lcbn == 2) return d.res_dev ? wino_launch_instance<RING, 1, 2, true>(a, blocks, stream)
+                                  : wino_launch_instance<RING, 1, 2, false>(a, blocks, stream);
+  return d.res_dev ? wino_launch_instance<RING, 1, 1, true>(a, blocks, stream)
+                   : wino_launch_instance<RING, 1, 1, false>(a, blocks, stream);
+}
+
+int wino_conv_launch(const StConvDesc& d, hipStream_t stream, bool narrow, bool parent_sched) {
+  WinoArgs a;
+  long long blocks = 0;
+  ST_CHECK(wino_fill_args(d, narrow, a, &blocks));
   int rc;
-  if (ktail && cbn == 2 && !d.res_dev) rc = wino_launch_instance<2, 2, false, true>(a, (unsigned)blocks, stream);
-  else if (ktail && cbn == 1 && lcbn == 1 && !d.res_dev) rc = wino_launch_instance<1, 1, false, true>(a, (unsigned)blocks, stream);
-  else if (cbn == 2) rc = d.res_dev ? wino_launch_instance<2, 2, true>(a, (unsigned)blocks, stream)
-                               : wino_launch_instance<2, 2, false>(a, (unsigned)blocks, stream);
-  else if (lcbn == 2) rc = d.res_dev ? wino_launch_instance<1, 2, true>(a, (unsigned)blocks, stream)
-                                     : wino_launch_instance<1, 2, false>(a, (unsigned)blocks, stream);
-  else rc = d.res_dev ? wino_launch_instance<1, 1, true>(a, (unsigned)blocks, stream)
-                      : wino_launch_instance<1, 1, false>(a, (unsigned)blocks, stream);
+#ifdef ST_ABLATION
+  if (parent_sched || !wn_ring()) rc = wino_conv_dispatch<false>(d, a, (unsigned)blocks, narrow, stream);
+  else
+#else
+  ST_REQUIRE(!parent_sched, "winograd conv: the schedule before the weight ring exists in the tools build only");
+#endif
+    rc = wino_conv_dispatch<true>(d, a, (unsigned)blocks, narrow, stream);
   ST_CHECK(rc);
   ST_CHECK_HIP(hipGetLastError());
   return ST_OK;
@@ -776,8 +1040,16 @@ int wino_group_launch(const StConvDesc* d, int n, hipStream_t stream) {
   for (int k = n; k <= WN_GROUP_MAX; ++k) g.first[k] = (unsigned)total;
   constexpr int lds = wn_lds_floats(2) * (int)sizeof(float);
   static int lds_set = 0;
-  auto kern = wino_conv3x3_group_kernel<2, 2>;
+  auto kern = wino_conv3x3_group_kernel;
   ST_ENSURE_DYNAMIC_LDS(kern, lds, lds_set);
+#ifdef ST_ABLATION
+  if (!wn_ring()) {
+    static int lds_set_parent = 0;
+    auto kern_parent = wino_conv3x3_group_kernel_parent;
+    ST_ENSURE_DYNAMIC_LDS(kern_parent, lds, lds_set_parent);
+    hipLaunchKernelGGL(kern_parent, dim3((unsigned)total), dim3(256), lds, stream, g);
+  } else
+#endif
   hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), lds, stream, g);
   ST_CHECK_HIP(hipGetLastError());
   return ST_OK;

@@ -42,6 +42,9 @@ constexpr int CT_RB_FLOATS = 4 * 2 * 32 * 32;                // [a][j][tile][co]
 constexpr int CT_WF_FLOATS = 64 * 64;
 constexpr int CT_LDS_FLOATS = CT_WIN_FLOATS + CT_RB_FLOATS + CT_WF_FLOATS + 64;
 constexpr int CT_NPW = (CT_PIECES + 3) / 4;                  // DMA pieces per wave
+// final epilogue: a lane stores CT_OUT_PT pixel tiles x CT_OUT_CB cout blocks of 16, one b128 store each - the youngest
+// memory operations of a block, which the next block's first wait leaves in flight
+constexpr int CT_OUT_PT = 2, CT_OUT_CB = 4, CT_OUT_STORES = CT_OUT_PT * CT_OUT_CB;
 
 struct TailArgs {
   const float* in;      // conv2 input (bottleneck conv1 output), 32 channels
@@ -158,7 +161,8 @@ __global__ __launch_bounds__(256, 2) void wino_csp_tail_kernel(const TailArgs p)
     // window of `blk` landed (this wave's pieces), previous block's stores retired; every wave is past its last LDS
     // read of the previous block (operand tiles alias Rb) and, the first time, Wf / Bf are written
     // (the previous block's 8 output stores are the youngest memory operations of the wave: vmcnt(8) leaves them in flight)
-    asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+    static_assert(CT_OUT_STORES == 8, "one b128 store per (pixel tile, cout block of 16) of the final epilogue below");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(CT_OUT_STORES) : "memory");
     __syncthreads();
     const int bx = (int)(blk % (unsigned)p.tbx);
     const unsigned rr = blk / (unsigned)p.tbx;
@@ -317,9 +321,9 @@ __global__ __launch_bounds__(256, 2) void wino_csp_tail_kernel(const TailArgs p)
     __builtin_amdgcn_s_setprio(2);
     // ---- final epilogue: lane = pixel 16 pt + i16, accumulator = couts 16 cb + 4 kq .. + 3
 #pragma unroll
-    for (int pt = 0; pt < 2; ++pt)
+    for (int pt = 0; pt < CT_OUT_PT; ++pt)
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
+      for (int cb = 0; cb < CT_OUT_CB; ++cb) {   // CT_OUT_STORES stores: the loop's wait above counts them
         f32x4 v = acc2[pt][cb];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = wn_silu(v[e]);
