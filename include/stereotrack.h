@@ -577,6 +577,30 @@ int st_tracker_num_tracks(const StTracker* t);
 long long st_tracker_next_id(const StTracker* t);
 int st_tracker_get_track(const StTracker* t, int index, int64_t* id, double* mean8, double* cov64,
                          int* tentative, int* tracked, int* last_frame);
+/* EVERYTHING a track knows (tests/test_cpu_tracker_state.py, tests/test_tracker_state_gpu.py): the fields the host
+ * tracker's tracks and the device tracker's (section 9) share, in one layout, so that the two can be compared field for
+ * field.  mean / cov: the float64 Kalman state; saved_*: the filter observation-centric recovery restores (all zero
+ * until the track's first predict as a confirmed, tracked track); win / win_valid: the last win_len <= vel_delta_t + 1
+ * entries of the observation history, OLDEST FIRST (win_valid 0 = the frame had no detection for the track: that row is
+ * zero), slots >= win_len zero; n_obs: entries ever pushed; last_valid: the last detection; trailing_none: frames
+ * since; vel: the velocity direction (dy, dx), vel_placeholder: it is the (-1, -1) "no velocity yet" value. */
+#define ST_TRACK_WINDOW 8
+typedef struct StTrackState {
+  int struct_size;
+  int tentative, tracked, last_frame, n_fed, win_len, trailing_none, vel_placeholder;
+  int64_t id;
+  int64_t n_obs;
+  double mean[8], cov[64], saved_mean[8], saved_cov[64];
+  float win[ST_TRACK_WINDOW][4];
+  int win_valid[ST_TRACK_WINDOW];
+  float last_valid[4];
+  float vel[2];
+} StTrackState;
+/* All live tracks in creation order -> out[0 .. *out_n), *next_id = the id the next new track gets.  Read-only.
+ * struct_size = sizeof(StTrackState) of the caller.  cap < live tracks, or a tracker whose window (vel_delta_t + 1) is
+ * longer than ST_TRACK_WINDOW: ST_ERR_INVALID. */
+int st_tracker_get_states(const StTracker* t, StTrackState* out, int cap, int struct_size, int* out_n,
+                          long long* next_id);
 
 
 /* ------------------------------------------------------------------------
@@ -603,6 +627,14 @@ size_t st_batched_tracker_scratch_bytes(const StBatchedTracker* t);
 int st_batched_tracker_step(StBatchedTracker* t, const int32_t* frame_ids_dev, const float* dets_dev,
                             const int32_t* counts_dev, void* state_dev, void* scratch_dev, float* out_rows_dev,
                             int64_t* out_ids_dev, int32_t* out_counts_dev, int32_t* status_dev, st_stream_t stream);
+/* State read-back of sequence b from the caller's state_dev (tests): the live tracks in slot (= creation) order ->
+ * out_host[0 .. *n_tracks) (HOST memory, the StTrackState of section 8), *next_id, *status = the sequence's sticky
+ * status.  The copies are enqueued on `stream`, i.e. after the steps already enqueued there, and the call waits for
+ * them; state_dev is only read.  A sequence with a non-zero status reports it with *n_tracks = 0 (its slots are not a
+ * tracker state any more).  cap < live tracks: ST_ERR_INVALID. */
+int st_batched_tracker_get_states(const StBatchedTracker* t, const void* state_dev, int b, StTrackState* out_host,
+                                  int cap, int struct_size, int* n_tracks, long long* next_id, int* status,
+                                  st_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 10. Mesh-Affine camera-motion compensation (CMC) of the tracker (reference OCSORTTracker_Disparity(cmc=dict(

@@ -64,6 +64,46 @@ def tracker_config(obj_score_thr, init_track_thr, weight_iou_with_det_scores, ma
                            float(vel_consist_weight), int(vel_delta_t), int(num_frames_retain))
 
 
+TRACK_WINDOW = 8      # ST_TRACK_WINDOW
+
+
+class StTrackState(C.Structure):
+    """Everything a track knows (include/stereotrack.h section 8), the same layout from the host tracker
+    (st_tracker_get_states) and from the device tracker (st_batched_tracker_get_states)."""
+    _fields_ = [
+        ('struct_size', C.c_int), ('tentative', C.c_int), ('tracked', C.c_int), ('last_frame', C.c_int),
+        ('n_fed', C.c_int), ('win_len', C.c_int), ('trailing_none', C.c_int), ('vel_placeholder', C.c_int),
+        ('id', C.c_int64), ('n_obs', C.c_int64),
+        ('mean', C.c_double * 8), ('cov', (C.c_double * 8) * 8),
+        ('saved_mean', C.c_double * 8), ('saved_cov', (C.c_double * 8) * 8),
+        ('win', (C.c_float * 4) * TRACK_WINDOW), ('win_valid', C.c_int * TRACK_WINDOW),
+        ('last_valid', C.c_float * 4), ('vel', C.c_float * 2),
+    ]
+
+
+TRACK_STATE_FIELDS = tuple(name for name, _ in StTrackState._fields_[1:])
+
+
+def track_state_dicts(buf, n):
+    """The first n StTrackState of a ctypes array -> [{field: int / bool / numpy array (a copy)}], the format of
+    OCSORTTracker_Disparity.track_states() and BatchedGpuTracker.track_states()."""
+    import numpy as np
+    out = []
+    for i in range(n):
+        s, d = buf[i], {}
+        for name in TRACK_STATE_FIELDS:
+            v = getattr(s, name)
+            if isinstance(v, C.Array):
+                v = np.ctypeslib.as_array(v).copy()
+            elif name in ('tentative', 'tracked', 'vel_placeholder'):
+                v = bool(v)
+            else:
+                v = int(v)
+            d[name] = v
+        out.append(d)
+    return out
+
+
 class StCmcParams(C.Structure):
     _fields_ = [('struct_size', C.c_int), ('step', C.c_int), ('winsize', C.c_int), ('ransac_thr', C.c_float),
                 ('min_inlier_ratio', C.c_float)]
@@ -234,6 +274,9 @@ _PROTOS = {
     'st_tracker_num_tracks': (_i, [_vp]),
     'st_tracker_next_id': (C.c_longlong, [_vp]),
     'st_tracker_get_track': (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    'st_tracker_get_states': (_i, [_vp, _vp, _i, _i, C.POINTER(_i), C.POINTER(C.c_longlong)]),
+    'st_batched_tracker_get_states': (_i, [_vp, _vp, _i, _vp, _i, _i, C.POINTER(_i), C.POINTER(C.c_longlong),
+                                           C.POINTER(_i), _vp]),
     'st_batched_tracker_create': (_i, [C.POINTER(StTrackerConfig), _i, _i, _i, C.POINTER(_vp)]),
     'st_batched_tracker_destroy': (_i, [_vp]),
     'st_batched_tracker_state_bytes': (_sz, [_vp]),

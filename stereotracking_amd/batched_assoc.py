@@ -56,6 +56,23 @@ class BatchedGpuTracker:
     def reset(self):
         self.state.zero_()
 
+    def sequence_state(self, b):
+        """Read-back of sequence b (st_batched_tracker_get_states; tests): (header, tracks).  header = dict(n_tracks,
+        next_id, status: the sequence's sticky status); tracks = the live tracks in creation order, the list of dicts
+        of OCSORTTracker_Disparity.track_states().  Ordered after the steps already enqueued on the current stream; one
+        host sync; the device state is only read.  A sequence with a non-zero status has no tracks to report."""
+        buf = (_lib.StTrackState * self.max_tracks)()
+        n, nxt, st = C.c_int(), C.c_longlong(), C.c_int()
+        check(self.lib.st_batched_tracker_get_states(self.handle, ptr(self.state), int(b), C.cast(buf, C.c_void_p),
+                                                     self.max_tracks, C.sizeof(_lib.StTrackState), C.byref(n),
+                                                     C.byref(nxt), C.byref(st), current_stream()),
+              'st_batched_tracker_get_states')
+        return (dict(n_tracks=n.value, next_id=nxt.value, status=st.value), _lib.track_state_dicts(buf, n.value))
+
+    def track_states(self, b):
+        """The live tracks of sequence b: sequence_state(b)[1]."""
+        return self.sequence_state(b)[1]
+
     def step(self, frame_ids, dets, counts, check_status=True):
         """frame_ids (batch,) int32, dets (batch, max_dets, 8) float32, counts (batch,) int32 - CUDA tensors.
         check_status: one host sync to raise on a capacity overflow (False: read `self.status` yourself).  A non-zero

@@ -10,7 +10,9 @@
 // (tests/test_batched_assoc_gpu.py): the association arithmetic is the same single IEEE operations in the same order
 // (float32 boxes / IoU / direction term, float64 Kalman filter and assignment; the file is built with
 // -ffp-contract=off), the assignment walks the same comparisons in the same order.  One documented last-bit
-// difference: acosf (ocml here, glibc on the host: <= 1 ulp on the direction term).
+// difference: acosf (ocml here, glibc on the host: <= 1 ulp on the direction term).  The per-track state (Kalman mean /
+// covariance, the saved filter, observation window, velocity direction: st_batched_tracker_get_states) is held EQUAL
+// to the host routine's on the bits after every step by tests/test_tracker_state_gpu.py.
 //
 // Why a wave per sequence.  One sequence is a SEQUENTIAL algorithm (the north_star keeps it on the CPU, and for one
 // video the CPU wins: 0.05 ms per frame).  The GPU form pays when there are hundreds of short sequences per step
@@ -214,7 +216,10 @@ __device__ void init_track(DTrack& t, long long id, const float* row, int frame_
   float m[4];
   xyxy_to_cxcyah(row, m);
   kf_initiate(m, t.kf);
-  t.saved = t.kf;
+  // no saved filter yet (the reference's track has no such item until its first predict as a tracked, confirmed
+  // track): zero, as the host tracker's value-initialised Track::saved, so that the two states compare equal
+  for (int i = 0; i < 8; ++i) t.saved.mean[i] = 0.0;
+  for (int i = 0; i < 64; ++i) t.saved.cov[i] = 0.0;
   push_obs(t, row, vel_delta_t);
   t.tracked = 1;
 }
@@ -841,6 +846,56 @@ extern "C" size_t st_batched_tracker_state_bytes(const StBatchedTracker* t) {
 }
 extern "C" size_t st_batched_tracker_scratch_bytes(const StBatchedTracker* t) {
   return t ? t->scratch_stride * (size_t)t->batch : 0;
+}
+
+extern "C" int st_batched_tracker_get_states(const StBatchedTracker* t, const void* state_dev, int b,
+                                             StTrackState* out_host, int cap, int struct_size, int* n_tracks,
+                                             long long* next_id, int* status, st_stream_t stream) {
+  using namespace st;
+  static_assert(ST_TRACK_WINDOW == ba::WINCAP, "StTrackState holds the device window");
+  if (!t || !state_dev || !n_tracks) return set_error(ST_ERR_INVALID, "st_batched_tracker_get_states: null argument");
+  ST_REQUIRE(struct_size == (int)sizeof(StTrackState), "st_batched_tracker_get_states: struct_size mismatch");
+  ST_REQUIRE(b >= 0 && b < t->batch, "st_batched_tracker_get_states: sequence %d of a batch of %d", b, t->batch);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const char* seq = static_cast<const char*>(state_dev) + (size_t)b * t->state_stride;
+  ba::SeqHeader hdr;
+  ST_CHECK_HIP(hipMemcpyAsync(&hdr, seq, sizeof(hdr), hipMemcpyDeviceToHost, s));
+  ST_CHECK_HIP(hipStreamSynchronize(s));
+  if (status) *status = hdr.poisoned;
+  if (next_id) *next_id = hdr.num_tracks;
+  *n_tracks = 0;
+  if (hdr.poisoned != ba::kOk) return ST_OK;   // the slots of an overflowed sequence are not a tracker state
+  const int n = hdr.n_tracks;
+  ST_REQUIRE(n >= 0 && n <= t->cfg.max_tracks, "st_batched_tracker_get_states: header holds %d tracks (max_tracks %d): "
+             "not a state buffer of this tracker", n, t->cfg.max_tracks);
+  ST_REQUIRE(cap >= n && (n == 0 || out_host), "st_batched_tracker_get_states: capacity %d < %d live tracks", cap, n);
+  if (n == 0) return ST_OK;
+  std::unique_ptr<ba::DTrack[]> tracks(new ba::DTrack[n]);
+  ST_CHECK_HIP(hipMemcpyAsync(tracks.get(), seq + sizeof(ba::SeqHeader), sizeof(ba::DTrack) * (size_t)n,
+                              hipMemcpyDeviceToHost, s));
+  ST_CHECK_HIP(hipStreamSynchronize(s));
+  for (int k = 0; k < n; ++k) {
+    const ba::DTrack& d = tracks[k];
+    StTrackState& o = out_host[k];
+    std::memset(&o, 0, sizeof(o));
+    o.struct_size = (int)sizeof(StTrackState);
+    o.id = d.id;
+    o.tentative = d.tentative != 0; o.tracked = d.tracked != 0; o.last_frame = d.last_frame; o.n_fed = d.n_fed;
+    o.n_obs = d.n_obs; o.trailing_none = d.trailing_none; o.vel_placeholder = d.vel_placeholder != 0;
+    o.win_len = d.win_len;                       // reported as stored; only the copy below is clamped
+    std::memcpy(o.mean, d.kf.mean, sizeof(o.mean));
+    std::memcpy(o.cov, d.kf.cov, sizeof(o.cov));
+    std::memcpy(o.saved_mean, d.saved.mean, sizeof(o.saved_mean));
+    std::memcpy(o.saved_cov, d.saved.cov, sizeof(o.saved_cov));
+    for (int w = 0; w < std::min(std::max(d.win_len, 0), ba::WINCAP); ++w) {   // slots >= win_len: an earlier track's leftovers
+      std::memcpy(o.win[w], d.win[w], sizeof(o.win[w]));
+      o.win_valid[w] = d.win_valid[w] != 0;
+    }
+    std::memcpy(o.last_valid, d.last_valid, sizeof(o.last_valid));
+    o.vel[0] = d.vel[0]; o.vel[1] = d.vel[1];
+  }
+  *n_tracks = n;
+  return ST_OK;
 }
 
 extern "C" int st_batched_tracker_step(StBatchedTracker* t, const int32_t* frame_ids_dev, const float* dets_dev,

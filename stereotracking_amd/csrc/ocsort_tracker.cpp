@@ -19,9 +19,14 @@
 // can differ from the Python stack in the last bit and are documented rather than hidden: acosf (glibc vs the SLEEF
 // routine behind torch.acos: <= 1 ulp, i.e. <= 1e-8 on a cost) and the 4x4 Cholesky / 8x8 products of the Kalman
 // update (plain loops here, LAPACK / BLAS there: ~1e-16 relative on the state, invisible after the float32 cast
-// the cost matrix applies).  Exact ties (duplicate boxes) stay exact ties, because both sides of a tie go through
+// the cost matrix applies).  A third, found by the state tests: sqrtf here is correctly rounded, torch.sqrt on the CPU is
+// not (1 ulp off on ~0.5 % of inputs); the Python backend takes the root of the STORED velocity direction through
+// float64 so that the states agree on the bits, the root inside its cost matrix stays torch's (<= 1 ulp on the
+// direction term, like acosf).  Exact ties (duplicate boxes) stay exact ties, because both sides of a tie go through
 // identical instructions.  tests/test_cpu_tracker_oracle.py holds the ids, boxes, scores, depth and scales of
-// every frame EQUAL to the oracle's and the Kalman state equal to 1e-9.
+// every frame EQUAL to the oracle's and the Kalman state equal to 1e-9.  tests/test_cpu_tracker_state.py holds the
+// WHOLE per-track state (st_tracker_get_states) bit-equal to the Python backend driven by these very loops restated
+// in Python floats (tests/kalman_ref.py), and those loops to mpmath within 4 x the error of the numpy filter.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -566,5 +571,40 @@ extern "C" int st_tracker_get_track(const StTracker* t, int index, int64_t* id, 
   if (tentative) *tentative = k.tentative;
   if (tracked) *tracked = k.tracked;
   if (last_frame) *last_frame = k.last_frame;
+  return ST_OK;
+}
+
+extern "C" int st_tracker_get_states(const StTracker* t, StTrackState* out, int cap, int struct_size, int* out_n,
+                                     long long* next_id) {
+  using namespace st;
+  if (!t || !out_n) return set_error(ST_ERR_INVALID, "st_tracker_get_states: null argument");
+  ST_REQUIRE(struct_size == (int)sizeof(StTrackState), "st_tracker_get_states: struct_size mismatch");
+  const int n = (int)t->tracks.size();
+  ST_REQUIRE(cap >= n && (n == 0 || out), "st_tracker_get_states: capacity %d < %d live tracks", cap, n);
+  for (int k = 0; k < n; ++k) {
+    const Track& s = t->tracks[k];
+    ST_REQUIRE(s.win.size() <= (size_t)ST_TRACK_WINDOW,
+               "st_tracker_get_states: track %lld keeps a window of %zu observations (vel_delta_t + 1), StTrackState "
+               "holds %d", (long long)s.id, s.win.size(), ST_TRACK_WINDOW);
+    StTrackState& o = out[k];
+    std::memset(&o, 0, sizeof(o));
+    o.struct_size = (int)sizeof(StTrackState);
+    o.id = s.id;
+    o.tentative = s.tentative; o.tracked = s.tracked; o.last_frame = s.last_frame; o.n_fed = s.n_fed;
+    o.n_obs = s.n_obs; o.win_len = (int)s.win.size(); o.trailing_none = s.trailing_none;
+    o.vel_placeholder = s.vel_is_placeholder;
+    std::memcpy(o.mean, s.kf.mean, sizeof(o.mean));
+    std::memcpy(o.cov, s.kf.cov, sizeof(o.cov));
+    std::memcpy(o.saved_mean, s.saved.mean, sizeof(o.saved_mean));
+    std::memcpy(o.saved_cov, s.saved.cov, sizeof(o.saved_cov));
+    for (size_t w = 0; w < s.win.size(); ++w) {
+      std::memcpy(o.win[w], s.win[w].v, sizeof(o.win[w]));
+      o.win_valid[w] = s.win_valid[w] != 0;
+    }
+    std::memcpy(o.last_valid, s.last_valid.v, sizeof(o.last_valid));
+    o.vel[0] = s.vel[0]; o.vel[1] = s.vel[1];
+  }
+  *out_n = n;
+  if (next_id) *next_id = t->num_tracks;
   return ST_OK;
 }

@@ -211,6 +211,50 @@ class OCSORTTracker_Disparity:
                             last_frame=lf.value))
         return out
 
+    def track_states(self):
+        """EVERYTHING the live tracks know, in creation order: a list of dicts with the fields of StTrackState
+        (include/stereotrack.h section 8; _lib.TRACK_STATE_FIELDS) - the same format from both backends and from
+        BatchedGpuTracker.track_states(b).  Native: st_tracker_get_states.  Python: derived from the _Track items (the
+        window = the last vel_delta_t + 1 entries of `obs`, a None entry = a zero row with win_valid 0; `saved` None =
+        zeros)."""
+        if self.backend == 'native':
+            lib, h = _lib.load(), self._handle()
+            n = lib.st_tracker_num_tracks(h)
+            buf = (_lib.StTrackState * max(n, 1))()
+            k, nxt = C.c_int(), C.c_longlong()
+            _lib.check(lib.st_tracker_get_states(h, C.cast(buf, C.c_void_p), n, C.sizeof(_lib.StTrackState),
+                                                 C.byref(k), C.byref(nxt)), 'st_tracker_get_states')
+            return _lib.track_state_dicts(buf, k.value)
+        cap = self.vel_delta_t + 1
+        if cap > _lib.TRACK_WINDOW:
+            raise ValueError(f'track_states holds a window of {_lib.TRACK_WINDOW} observations, vel_delta_t + 1 = {cap}')
+        out = []
+        for tid, t in self.tracks.items():
+            recent = t.obs[-cap:]
+            win = np.zeros((_lib.TRACK_WINDOW, 4), np.float32)
+            win_valid = np.zeros(_lib.TRACK_WINDOW, np.int32)
+            for k, box in enumerate(recent):
+                if box is not None:
+                    win[k], win_valid[k] = box[:4].float().numpy(), 1
+            trailing = 0
+            for box in reversed(t.obs):
+                if box is not None:
+                    break
+                trailing += 1
+            last = self._last_obs(t)
+            vel = t.velocity.float()
+            saved = t.saved if t.saved is not None else (np.zeros(8), np.zeros((8, 8)))
+            out.append(dict(
+                tentative=bool(t.tentative), tracked=bool(t.tracked), last_frame=t.last_frame,
+                n_fed=len(t.memo['bboxes']), win_len=len(recent), trailing_none=trailing,
+                vel_placeholder=bool(vel.sum() == -2), id=int(tid), n_obs=len(t.obs),
+                mean=np.array(t.mean, np.float64), cov=np.array(t.covariance, np.float64),
+                saved_mean=np.array(saved[0], np.float64), saved_cov=np.array(saved[1], np.float64),
+                win=win, win_valid=win_valid,
+                last_valid=np.zeros(4, np.float32) if last is None else last[:4].float().numpy().copy(),
+                vel=vel.numpy().copy()))
+        return out
+
     def track_records(self, frame_ids, records, cmc=None):
         """A CHUNK of frames in one native call (st_tracker_track_records): `records` = host float32 (F, M + 1, 13)
         frame records (pipeline.pack_detections(scaled='both')), `frame_ids` = F ints.
@@ -334,7 +378,12 @@ class OCSORTTracker_Disparity:
         cx1, cy1 = (b1[0] + b1[2]) / 2.0, (b1[1] + b1[3]) / 2.0
         cx2, cy2 = (b2[0] + b2[2]) / 2.0, (b2[1] + b2[3]) / 2.0
         speed = torch.stack([cy2 - cy1, cx2 - cx1])
-        return speed / (torch.sqrt(speed[0] ** 2 + speed[1] ** 2) + 1e-6)
+        # The square root as ONE correctly rounded float32 operation, which is what the native and the device tracker
+        # evaluate (sqrtf).  torch.sqrt on the CPU is a vector-library routine that is not correctly rounded (1 ulp off
+        # on 0.55 % of random inputs, DESIGN.md 2 "Per-track state"); the float64 root of a float32 rounds to the
+        # correctly rounded float32 root (53 >= 2 * 24 + 2 bits), so the stored direction is the same on the bits.
+        root = torch.tensor(math.sqrt(float(speed[0] ** 2 + speed[1] ** 2)), dtype=torch.float32)
+        return speed / (root + 1e-6)
 
     @staticmethod
     def _vel_direction_batch(b1, b2):
