@@ -1115,6 +1115,74 @@ int st_aflink_transform(const StAflinkArgs* args, st_stream_t stream);
 int st_aflink_score(const StAflinkArgs* args, const void* weights, st_stream_t stream);
 int st_aflink_run(const StAflinkArgs* args, const void* weights, st_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * 19. ECC camera-motion compensation (tracker option cmc=dict(method='ecc'); the reference's CameraMotionCompensation =
+ *     cv2.findTransformECC), csrc/cmc_ecc.hip.  The rules E0..E10 are restated from OpenCV 4.x ecc.cpp
+ *     [upstream-memory], listed in tests/ecc_ref.py and DESIGN.md "ECC camera-motion compensation"; parity with cv2 is
+ *     unpinned.  The warps feed the tracker routines of section 10 (st_tracker_track_cmc, ..._records_cmc) unchanged.
+ *   plane    fp32 (plane_h, plane_w) = (img_h / downscale, img_w / downscale), st_cmc_ecc_plane_size.
+ *   front    frames -> planes (crop to (h, w), fixed-point grey of the BGR frame, downscale x downscale box mean),
+ *            from N separate uint8 (3, fh, fw) device frames (host array of device pointers) or a padded fp32
+ *            (N, 3, H, W) batch; both give the same bits.
+ *   prepare  planes -> blurred template, blurred input and its two gradients, each (N, plane_h, plane_w) fp32 (any
+ *            output may be null).  Test-facing.
+ *   step     ONE iteration from the given plane warps (N, 6) float64 {m00, m01, m02, m10, m11, m12} (null: identity)
+ *            -> (N, ST_ECC_STEP_DOUBLES) float64 at the ST_ECC_STEP_* offsets (H as 6 x 6 row-major, its top-left
+ *            K x K used; the warp in PLANE coordinates; fields behind a failure stay 0).  Test-facing, the same
+ *            launches as the estimate.
+ *   estimate plane pairs (prev[n] = template, curr[n] = input) -> warps (N, ST_CMC_WARP_FLOATS) = {valid, rho, 2 x 3
+ *            warp in IMAGE coordinates} (a failed estimate: {0, 0, identity}) and, optionally, the iterations run
+ *            (N,) int32.  All num_iters rounds are enqueued on `stream`; no host sync.  Bit-identical from run to run,
+ *            and a pair's row does not depend on N.
+ *   ws: caller-owned device workspace of st_cmc_ecc_workspace_bytes(N, plane_h, plane_w).
+ *   Every call refuses, before any launch (ST_ERR_INVALID, nothing written): a struct_size mismatch, a null pointer,
+ *   a short workspace, a warp_mode / downscale / gauss_filt_size outside its set, num_iters < 1, a plane side under 8
+ *   (and N outside 1..65535, a NaN stop_eps, num_iters > 1000 in the estimate: 2 launches are enqueued per round).
+ * ---------------------------------------------------------------------- */
+#define ST_ECC_TRANSLATION 0
+#define ST_ECC_EUCLIDEAN 1
+#define ST_ECC_AFFINE 2
+#define ST_ECC_STEP_DOUBLES 72
+#define ST_ECC_STEP_VALID 0
+#define ST_ECC_STEP_N 1
+#define ST_ECC_STEP_MEAN_I 2
+#define ST_ECC_STEP_MEAN_T 3
+#define ST_ECC_STEP_STD_I 4
+#define ST_ECC_STEP_STD_T 5
+#define ST_ECC_STEP_IMG_NORM 6
+#define ST_ECC_STEP_TMP_NORM 7
+#define ST_ECC_STEP_CORR 8
+#define ST_ECC_STEP_RHO 9
+#define ST_ECC_STEP_LAMBDA 10
+#define ST_ECC_STEP_H 12      /* 36 */
+#define ST_ECC_STEP_IP 48     /* 6 */
+#define ST_ECC_STEP_TP 54     /* 6 */
+#define ST_ECC_STEP_DP 60     /* 6 */
+#define ST_ECC_STEP_WARP 66   /* 6: the updated warp (the input warp after a failure) */
+typedef struct StEccParams {
+  int struct_size;        /* sizeof(StEccParams) */
+  int warp_mode;          /* ST_ECC_TRANSLATION / EUCLIDEAN / AFFINE (reference default EUCLIDEAN) */
+  int num_iters;          /* >= 1 (default 50) */
+  float stop_eps;         /* stop when |rho - last rho| < stop_eps (default 1e-3) */
+  int gauss_filt_size;    /* 1, 3 or 5 (default 1) */
+  int downscale;          /* 1, 2 or 4: plane = box mean of downscale x downscale grey pixels */
+} StEccParams;
+int st_cmc_ecc_plane_size(int img_h, int img_w, int downscale, int* plane_h, int* plane_w);
+size_t st_cmc_ecc_workspace_bytes(int N, int plane_h, int plane_w);
+int st_cmc_ecc_front_u8(const void* const* frames_u8_dev_ptrs_host, int N, int fh, int fw, int h, int w, int downscale,
+                        float* planes_dev, st_stream_t stream);
+int st_cmc_ecc_front_f32(const float* batch_dev, int N, int H, int W, int h, int w, int downscale, float* planes_dev,
+                         st_stream_t stream);
+int st_cmc_ecc_prepare(const float* prev_planes_dev, const float* curr_planes_dev, int N, int img_h, int img_w,
+                       const StEccParams* params, void* ws, size_t ws_bytes, float* tmpl_out_dev, float* input_out_dev,
+                       float* gx_out_dev, float* gy_out_dev, st_stream_t stream);
+int st_cmc_ecc_step(const float* prev_planes_dev, const float* curr_planes_dev, int N, int img_h, int img_w,
+                    const StEccParams* params, const double* warps_in_dev, void* ws, size_t ws_bytes,
+                    double* step_out_dev, st_stream_t stream);
+int st_cmc_ecc_estimate(const float* prev_planes_dev, const float* curr_planes_dev, int N, int img_h, int img_w,
+                        const StEccParams* params, void* ws, size_t ws_bytes, float* warps_out_dev, int* iters_out_dev,
+                        st_stream_t stream);
+
 /* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call

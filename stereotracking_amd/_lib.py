@@ -109,6 +109,11 @@ class StCmcParams(C.Structure):
                 ('min_inlier_ratio', C.c_float)]
 
 
+class StEccParams(C.Structure):
+    _fields_ = [('struct_size', C.c_int), ('warp_mode', C.c_int), ('num_iters', C.c_int), ('stop_eps', C.c_float),
+                ('gauss_filt_size', C.c_int), ('downscale', C.c_int)]
+
+
 class StSgbmParams(C.Structure):
     _fields_ = [('struct_size', C.c_int), ('num_disparities', C.c_int), ('block_size', C.c_int), ('P1', C.c_int),
                 ('P2', C.c_int), ('disp12_max_diff', C.c_int), ('uniqueness_ratio', C.c_int),
@@ -265,6 +270,13 @@ _PROTOS = {
     'st_cmc_estimate': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(StCmcParams), _vp, _sz, _vp, _vp, _vp, _vp]),
     'st_cmc_mesh_fit': (_i, [_vp, _i, _i, _i, C.POINTER(StCmcParams), _vp, _sz, _vp, _vp, _vp, _vp]),
     'st_cmc_fit': (_i, [_vp, _i, _i, C.c_float, C.c_float, _vp, _sz, _vp, _vp, _vp]),
+    'st_cmc_ecc_plane_size': (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    'st_cmc_ecc_workspace_bytes': (_sz, [_i, _i, _i]),
+    'st_cmc_ecc_front_u8': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'st_cmc_ecc_front_f32': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'st_cmc_ecc_prepare': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(StEccParams), _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    'st_cmc_ecc_step': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(StEccParams), _vp, _vp, _sz, _vp, _vp]),
+    'st_cmc_ecc_estimate': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(StEccParams), _vp, _sz, _vp, _vp, _vp]),
     'st_sgbm_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'st_sgbm_u8': (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(StSgbmParams), _vp, _sz, _vp, _i, _i, _vp, _vp]),
     'st_sgbm_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(StSgbmParams), _vp, _sz, _vp, _vp, _vp]),

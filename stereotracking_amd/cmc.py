@@ -1,4 +1,6 @@
-"""Mesh-Affine camera-motion compensation (CMC) of the tracker: the device half (estimate) and the host half (apply).
+"""Camera-motion compensation (CMC) of the tracker: the device half (estimate: Mesh-Affine, and ECC further down -
+csrc/cmc_ecc.hip, DESIGN.md "ECC camera-motion compensation") and the host half (apply).  The tracker and the MOT shell
+reach either estimate through one small object per method (`estimator(cmc)`: plane_shape, front, estimate).
 
 Reference: OCSORTTracker_Disparity(cmc=dict(method='glme_affine', glme=dict(step, winsize, ransac_thr,
 min_inlier_ratio))) - mmtrack/models/trackers/ocsort_tracker_disparity.py:62-97, gmc.py:7-45, utils.py:6-55.  The
@@ -163,6 +165,214 @@ def apply_warp(mean, cov, warp):
     M[3, 3] = s
     M[7, 7] = s
     return mean, M.dot(cov).dot(M.T)
+
+
+# ---- ECC (cmc=dict(method='ecc')): csrc/cmc_ecc.hip, rules in tests/ecc_ref.py and DESIGN.md -------------------------
+ECC_MODES = dict(MOTION_TRANSLATION=0, MOTION_EUCLIDEAN=1, MOTION_AFFINE=2)
+ECC_DEFAULTS = dict(warp_mode='MOTION_EUCLIDEAN', num_iters=50, stop_eps=1e-3, gauss_filt_size=1, downscale=2)
+ECC_STEP_DOUBLES = 72
+# field -> (offset, length) of one st_cmc_ecc_step row (include/stereotrack.h, ST_ECC_STEP_*)
+ECC_STEP_FIELDS = dict(valid=(0, 1), n=(1, 1), mean_i=(2, 1), mean_t=(3, 1), std_i=(4, 1), std_t=(5, 1),
+                       img_norm=(6, 1), tmp_norm=(7, 1), corr=(8, 1), rho=(9, 1), lam=(10, 1), H=(12, 36), iP=(48, 6),
+                       tP=(54, 6), dp=(60, 6), warp=(66, 6))
+
+
+def ecc_params(ecc=None):
+    """cmc['ecc'] overrides on the reference defaults (camera_motion_compensation.py:21-27; downscale is this
+    package's) -> dict; warp_mode comes back as its bare name ('cv2.MOTION_EUCLIDEAN' and 'MOTION_EUCLIDEAN' parse)."""
+    p = dict(ECC_DEFAULTS)
+    for k, v in (ecc or {}).items():
+        if k not in p:
+            raise ValueError(f"unknown ecc option '{k}' (expected one of {sorted(p)})")
+        p[k] = v
+    mode = p['warp_mode']
+    name = mode[len('cv2.'):] if isinstance(mode, str) and mode.startswith('cv2.') else mode
+    if name == 'MOTION_HOMOGRAPHY':
+        raise ValueError('ecc warp_mode MOTION_HOMOGRAPHY is not supported: the Kalman application takes a 2 x 3 warp')
+    if not isinstance(name, str) or name not in ECC_MODES:
+        raise ValueError(f"unknown ecc warp_mode {mode!r} (expected one of {sorted(ECC_MODES)})")
+    p['warp_mode'] = name
+    for k in ('num_iters', 'gauss_filt_size', 'downscale'):
+        if isinstance(p[k], bool) or int(p[k]) != p[k]:
+            raise ValueError(f'ecc {k} {p[k]!r} must be an integer')
+        p[k] = int(p[k])
+    if p['num_iters'] < 1:
+        raise ValueError(f"ecc num_iters {p['num_iters']} must be >= 1")
+    if p['gauss_filt_size'] not in (1, 3, 5):
+        raise ValueError(f"ecc gauss_filt_size {p['gauss_filt_size']} is not supported (1, 3 or 5)")
+    if p['downscale'] not in (1, 2, 4):
+        raise ValueError(f"ecc downscale {p['downscale']} is not supported (1, 2 or 4)")
+    p['stop_eps'] = float(p['stop_eps'])
+    if not p['stop_eps'] == p['stop_eps']:
+        raise ValueError('ecc stop_eps is NaN')
+    return p
+
+
+def ecc_plane_shape(h, w, downscale):
+    return int(h) // int(downscale), int(w) // int(downscale)
+
+
+def ecc_to_image(warp, downscale):
+    """Plane warp [A | t] (2 x 3) -> image warp: plane pixel i sits at image coordinate s i + c, c = (s - 1) / 2, so
+    t -> s t + c - A (c, c).  float64."""
+    M = np.asarray(warp, np.float64).reshape(2, 3)
+    c = (downscale - 1) / 2.0
+    return np.hstack([M[:, :2], (downscale * M[:, 2] + c - M[:, :2] @ np.array([c, c]))[:, None]])
+
+
+def _ecc_struct(p):
+    return _lib.StEccParams(C.sizeof(_lib.StEccParams), ECC_MODES[p['warp_mode']], p['num_iters'], p['stop_eps'],
+                            p['gauss_filt_size'], p['downscale'])
+
+
+def ecc_front(img, h, w, downscale=2, out=None):
+    """Grey fp32 planes (N, h // downscale, w // downscale) of N frames on the device: crop to (h, w), fixed-point grey,
+    downscale x downscale box mean.  img as front(): a (N, 3, H, W) fp32 / uint8 BGR CUDA batch or a list of N uint8
+    (1, 3, fh, fw) CUDA frames; both give the same bits."""
+    lib = _lib.load()
+    ph, pw = ecc_plane_shape(h, w, downscale)
+    if isinstance(img, (list, tuple)):
+        fr = [f.contiguous() for f in img]
+        if any(f.dtype != torch.uint8 or f.dim() != 4 or f.shape[:2] != (1, 3) or f.shape != fr[0].shape for f in fr):
+            raise ValueError('ECC front: frames must be uint8 (1, 3, h, w) tensors of one size')
+        N, fh, fw = len(fr), int(fr[0].shape[-2]), int(fr[0].shape[-1])
+        out = torch.empty(N, ph, pw, device=fr[0].device) if out is None else out
+        ptrs = (C.c_void_p * N)(*[f.data_ptr() for f in fr])
+        check(lib.st_cmc_ecc_front_u8(ptrs, N, fh, fw, int(h), int(w), int(downscale), ptr(out), current_stream()),
+              'st_cmc_ecc_front_u8')
+        return out
+    if img.dim() != 4 or img.shape[1] < 3 or not img.is_cuda:
+        raise ValueError('ECC front: img must be a (N, 3, H, W) CUDA tensor')
+    N, H, W = int(img.shape[0]), int(img.shape[2]), int(img.shape[3])
+    if img.dtype == torch.uint8:
+        return ecc_front([img[i:i + 1, :3] for i in range(N)], h, w, downscale, out)
+    out = torch.empty(N, ph, pw, device=img.device) if out is None else out
+    x = img[:, :3].float().contiguous()
+    check(lib.st_cmc_ecc_front_f32(ptr(x), N, H, W, int(h), int(w), int(downscale), ptr(out), current_stream()),
+          'st_cmc_ecc_front_f32')
+    return out
+
+
+def _ecc_planes(prev, curr, img_h, img_w, p):
+    """The two contiguous plane batches, checked against the plane size the library derives from (img_h, img_w)."""
+    shape = ecc_plane_shape(img_h, img_w, p['downscale'])
+    for t in (prev, curr):
+        if t.dim() != 3 or tuple(t.shape[1:]) != shape or t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError(f'ECC: planes must be (N, {shape[0]}, {shape[1]}) fp32 CUDA tensors, got {tuple(t.shape)} '
+                             f'{t.dtype}')
+    if prev.shape[0] != curr.shape[0]:
+        raise ValueError('ECC: template and input batches differ in N')
+    return prev.contiguous(), curr.contiguous(), int(prev.shape[0]), shape
+
+
+def ecc_workspace(n, plane_shape, dev):
+    return torch.empty(int(_lib.load().st_cmc_ecc_workspace_bytes(int(n), int(plane_shape[0]), int(plane_shape[1]))),
+                       dtype=torch.uint8, device=dev)
+
+
+def ecc_prepare(prev, curr, img_h, img_w, params=None, ws=None):
+    """Rules E1 / E2 -> (blurred template, blurred input, gx, gy), each (N, ph, pw) fp32.  Test-facing."""
+    p = ecc_params(params)
+    prev, curr, N, shape = _ecc_planes(prev, curr, img_h, img_w, p)
+    ws = ecc_workspace(N, shape, prev.device) if ws is None else ws
+    outs = [torch.empty_like(prev) for _ in range(4)]
+    prm = _ecc_struct(p)
+    check(_lib.load().st_cmc_ecc_prepare(ptr(prev), ptr(curr), N, int(img_h), int(img_w), C.byref(prm), ptr(ws),
+                                         ws.numel(), *[ptr(o) for o in outs], current_stream()), 'st_cmc_ecc_prepare')
+    return tuple(outs)
+
+
+def ecc_step(prev, curr, img_h, img_w, params=None, warps=None, ws=None):
+    """ONE iteration (rules E3 .. E8) from the plane warps `warps` ((N, 2, 3) float64, None: identity) -> (N, 72)
+    float64 device tensor; ecc_step_fields() names its columns.  Test-facing, the launches of ecc_estimate."""
+    p = ecc_params(params)
+    prev, curr, N, shape = _ecc_planes(prev, curr, img_h, img_w, p)
+    ws = ecc_workspace(N, shape, prev.device) if ws is None else ws
+    win = None
+    if warps is not None:
+        win = torch.as_tensor(np.asarray(warps, np.float64).reshape(N, 6)).to(prev.device)
+    out = torch.empty(N, ECC_STEP_DOUBLES, dtype=torch.float64, device=prev.device)
+    prm = _ecc_struct(p)
+    check(_lib.load().st_cmc_ecc_step(ptr(prev), ptr(curr), N, int(img_h), int(img_w), C.byref(prm), ptr(win), ptr(ws),
+                                      ws.numel(), ptr(out), current_stream()), 'st_cmc_ecc_step')
+    return out
+
+
+def ecc_step_fields(row, warp_mode='MOTION_EUCLIDEAN'):
+    """One host row of ecc_step() -> dict (H (K, K), iP / tP / dp (K,), warp (2, 3), scalars as floats)."""
+    row = np.asarray(row, np.float64)
+    K = (2, 3, 6)[ECC_MODES[warp_mode]]
+    d = {}
+    for k, (o, n) in ECC_STEP_FIELDS.items():
+        d[k] = float(row[o]) if n == 1 else row[o:o + n].copy()
+    d['H'] = d['H'].reshape(6, 6)[:K, :K]
+    for k in ('iP', 'tP', 'dp'):
+        d[k] = d[k][:K]
+    d['warp'] = d['warp'].reshape(2, 3)
+    d['valid'], d['n'] = bool(d['valid']), int(d['n'])
+    return d
+
+
+def ecc_estimate(prev, curr, img_h, img_w, params=None, with_iters=False, ws=None):
+    """ECC warps of the plane pairs (template prev[n], input curr[n]) on the device -> (N, 8) fp32 device tensor
+    [valid, rho, 2 x 3 warp in image coordinates] (+ the iterations run, (N,) int32, with with_iters).  Every round is
+    enqueued on the current stream; the host does not wait."""
+    p = ecc_params(params)
+    prev, curr, N, shape = _ecc_planes(prev, curr, img_h, img_w, p)
+    ws = ecc_workspace(N, shape, prev.device) if ws is None else ws
+    warps = torch.empty(N, WARP_FLOATS, device=prev.device)
+    iters = torch.empty(N, dtype=torch.int32, device=prev.device) if with_iters else None
+    prm = _ecc_struct(p)
+    check(_lib.load().st_cmc_ecc_estimate(ptr(prev), ptr(curr), N, int(img_h), int(img_w), C.byref(prm), ptr(ws),
+                                          ws.numel(), ptr(warps), ptr(iters), current_stream()), 'st_cmc_ecc_estimate')
+    return (warps, iters) if with_iters else warps
+
+
+# ---- one estimator object per method: what the tracker and the MOT shell call ------------------------------------------
+class MeshAffineEstimator:
+    """cmc=dict(method='glme_affine', glme=...): equalised 255 x 255 uint8 planes, Farneback flow, consensus fit."""
+    mode, plane_dtype = 'mesh_affine', torch.uint8
+
+    def __init__(self, options=None):
+        self.params = glme_params(options)
+
+    def plane_shape(self, h, w):
+        return SIDE, SIDE
+
+    def front(self, img, h, w, out=None):
+        return front(img, h, w, out=out)
+
+    def estimate(self, prev, curr, h, w):
+        return estimate(prev, curr, h, w, self.params)
+
+
+class EccEstimator:
+    """cmc=dict(method='ecc', ecc=...): fp32 grey planes of the frame / downscale, ECC iterations."""
+    mode, plane_dtype = 'ecc', torch.float32
+
+    def __init__(self, options=None):
+        self.params = ecc_params(options)
+
+    def plane_shape(self, h, w):
+        return ecc_plane_shape(h, w, self.params['downscale'])
+
+    def front(self, img, h, w, out=None):
+        return ecc_front(img, h, w, self.params['downscale'], out=out)
+
+    def estimate(self, prev, curr, h, w):
+        return ecc_estimate(prev, curr, h, w, self.params)
+
+
+def estimator(cmc):
+    """The tracker option cmc=dict(method=..., <method's options>) -> estimator object, None when CMC is off."""
+    method = cmc.get('method') if cmc is not None else None
+    if method is None:
+        return None
+    if method == 'glme_affine':
+        return MeshAffineEstimator(cmc.get('glme'))
+    if method == 'ecc':
+        return EccEstimator(cmc.get('ecc'))
+    raise ValueError(f"Unknown cmc method '{method}', expected 'glme_affine', 'ecc' or None.")
 
 
 class CmcFrame:

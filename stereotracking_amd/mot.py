@@ -35,6 +35,7 @@ from . import sgbm as _sgbm  # noqa: F401  (registers StereoSGBM)
 from . import coco_metric as _coco_metric  # noqa: F401  (registers CocoMetric in METRICS)
 from . import kitti_metrics as _kitti_metrics  # noqa: F401  (registers MOTKittiMetrics in METRICS)
 from . import tracklets as _tracklets  # noqa: F401  (registers InterpolateTracklets in TASK_UTILS)
+from . import camera_motion as _camera_motion  # noqa: F401  (registers CameraMotionCompensation in TASK_UTILS)
 
 
 def stack_batch(tensors, pad_size_divisor=0, pad_value=0):
@@ -486,13 +487,14 @@ class OCSORT_Disparity(nn.Module):
         self.timings['submit_s'] += time.perf_counter() - ts
         st['jobs'][ci] = dict(s=s, e=e, ev=ev, cmc=cmc, **holder)
 
-    # ---- camera-motion compensation of the tracker (cmc=dict(method='glme_affine')) ---------------------------------
+    # ---- camera-motion compensation of the tracker (cmc=dict(method='glme_affine' | 'ecc')) -------------------------
     def _cmc_submit(self, st, s, e):
         """On a side stream, from the chunk's input already on the device: the grey planes of frames [s, e) and the
         SPECULATIVE warps of the consecutive pairs (n - 1, n) (the first frame's pair reaches back to the last frame of
         the chunk submitted before).  The warps travel to the host beside the chunk's records; the association uses
         one only when its pair is (previous CMC image, frame) - see _cmc_track_records."""
         from . import cmc
+        est = self.tracker.cmc_estimator
         dev, img = st['dev'], st['img']
         metas = [st['data_samples'][n].metainfo for n in range(s, e)]
         shapes = {tuple(int(v) for v in m['img_shape'][:2]) for m in metas}
@@ -507,15 +509,15 @@ class OCSORT_Disparity(nn.Module):
         tail = self._staging.get('cmc_tail')                  # (planes, index, frame id, img_shape) of the last chunk
         k = e - s
         with torch.cuda.stream(cs):
-            planes = torch.empty(k + 1, cmc.SIDE, cmc.SIDE, dtype=torch.uint8, device=dev)
-            cmc.front(img.frames[s:e] if isinstance(img, RawFrames) else img[s:e], hw[0], hw[1], out=planes[1:])
+            planes = torch.empty(k + 1, *est.plane_shape(hw[0], hw[1]), dtype=est.plane_dtype, device=dev)
+            est.front(img.frames[s:e] if isinstance(img, RawFrames) else img[s:e], hw[0], hw[1], out=planes[1:])
             if tail is not None and tail[3] == hw:
                 planes[0].copy_(tail[0][tail[1]])
                 src0 = tail[2]
             else:
                 planes[0].copy_(planes[1])
                 src0 = -2                                     # matches no frame: computed on demand if needed
-            warps = cmc.estimate(planes[:-1], planes[1:], hw[0], hw[1], self.tracker.cmc_params)
+            warps = est.estimate(planes[:-1], planes[1:], hw[0], hw[1])
             host = torch.empty(k, cmc.WARP_FLOATS, pin_memory=True)
             host.copy_(warps, non_blocking=True)
             ev = torch.cuda.Event()
@@ -524,7 +526,7 @@ class OCSORT_Disparity(nn.Module):
         return dict(planes=planes, host=host, ev=ev, fids=fids, warp_src=[src0] + fids[:-1], hw=hw, stream=cs)
 
     def _cmc_plane(self, job, fid):
-        """Grey plane (1, 255, 255) of frame `fid`: from the chunk, else the tracker's previous CMC image."""
+        """Grey plane (1, ph, pw) of frame `fid`: from the chunk, else the tracker's previous CMC image."""
         if fid in job['fids']:
             i = job['fids'].index(fid) + 1
             return job['planes'][i:i + 1]
@@ -535,15 +537,14 @@ class OCSORT_Disparity(nn.Module):
     def _cmc_track_records(self, fids, chunk_np, job):
         """The chunk's association in native calls (st_tracker_track_records_cmc): a frame whose speculative pair is
         not (previous CMC image, frame) stops the call; that pair is estimated on demand and the call resumes there."""
-        from . import cmc
         trk = self.tracker
         warps = job['host'].numpy().copy()
         src = np.asarray(job['warp_src'], np.int32)
 
         def on_demand(f, prev_fid):
             with torch.cuda.stream(job['stream']):     # the copy too: it must follow the estimate on the CMC stream
-                w = cmc.estimate(self._cmc_plane(job, prev_fid), job['planes'][f + 1:f + 2], job['hw'][0], job['hw'][1],
-                                 trk.cmc_params)
+                w = trk.cmc_estimator.estimate(self._cmc_plane(job, prev_fid), job['planes'][f + 1:f + 2], job['hw'][0],
+                                               job['hw'][1])
                 return w[0].cpu().numpy()
 
         out = trk.track_records(fids, chunk_np, cmc=(warps, src, on_demand))

@@ -109,17 +109,14 @@ class OCSORTTracker_Disparity:
         self.num_frames_retain = num_frames_retain
         if momentums is not None:
             raise NotImplementedError('momentum buffers are not used by the stereo configs')
-        # Mesh-Affine camera-motion compensation (reference :62-76): estimated on the device (cmc.py,
-        # csrc/cmc_flow.hip), applied to the confirmed tracks' Kalman states right after the predict
+        # camera-motion compensation (reference :62-76): estimated on the device by the method's estimator (cmc.py:
+        # Mesh-Affine, csrc/cmc_flow.hip, or ECC, csrc/cmc_ecc.hip), applied to the confirmed tracks' Kalman states
+        # right after the predict
         self.cmc_cfg = cmc
-        method = cmc.get('method') if cmc is not None else None
-        if method is None:
-            self.cmc_mode = None
-        elif method == 'glme_affine':
-            self.cmc_mode = 'mesh_affine'
-            self.cmc_params = _cmc.glme_params(cmc.get('glme'))
-        else:
-            raise ValueError(f"Unknown cmc method '{method}', expected 'glme_affine' or None.")
+        self.cmc_estimator = _cmc.estimator(cmc)          # ValueError for an unknown method
+        self.cmc_mode = None if self.cmc_estimator is None else self.cmc_estimator.mode
+        if self.cmc_estimator is not None:
+            self.cmc_params = self.cmc_estimator.params
         self.reset_cmc()
         self.reset()
 
@@ -130,7 +127,7 @@ class OCSORTTracker_Disparity:
 
     def reset_cmc(self):
         """Forget the previous CMC image (the first frame of a video)."""
-        self.prev_cmc_img = None         # grey plane (1, 255, 255) uint8 on the device
+        self.prev_cmc_img = None         # grey plane (1, <the estimator's plane shape>) on the device
         self.prev_cmc_fid = -1
 
     def estimate_camera_motion(self, img, metainfo):
@@ -138,7 +135,8 @@ class OCSORTTracker_Disparity:
         previous CMC image.  img: the (1, 3, H, W) fp32 / uint8 CUDA batch the tracker receives (cropped to
         metainfo['img_shape']), or a cmc.CmcFrame of the shell's chunk path (plane computed with its chunk, with the
         speculative warp of the pair (warp_src, this frame), used when warp_src is the previous CMC image)."""
-        if self.cmc_mode != 'mesh_affine':
+        est = self.cmc_estimator
+        if est is None:
             return None
         fid = int(metainfo.get('frame_id', -1))
         h, w = (int(v) for v in metainfo['img_shape'][:2])
@@ -147,13 +145,13 @@ class OCSORTTracker_Disparity:
         else:
             if img is None:
                 raise ValueError('the tracker has CMC on: track() needs the frame (img)')
-            plane = _cmc.front(img[:1], h, w)
+            plane = est.front(img[:1], h, w)
         warp = None
         if self.prev_cmc_img is not None:
             if isinstance(img, _cmc.CmcFrame) and img.warp is not None and img.warp_src == self.prev_cmc_fid:
                 row = img.warp
             else:
-                row = _cmc.estimate(self.prev_cmc_img, plane, h, w, self.cmc_params)[0].cpu().numpy()
+                row = est.estimate(self.prev_cmc_img, plane, h, w)[0].cpu().numpy()
             warp = _cmc.warp_or_none(row)
         self.prev_cmc_img, self.prev_cmc_fid = plane, fid
         return warp
