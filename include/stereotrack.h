@@ -1184,6 +1184,40 @@ int st_cmc_ecc_estimate(const float* prev_planes_dev, const float* curr_planes_d
                         st_stream_t stream);
 
 /* ----------------------------------------------------------------------
+ * 20. Tracker-option sweeps on the batched GPU association (section 9): per-sequence tracker options, and a whole
+ *    recorded detection stream in ONE launch (stereotracking_amd.sweep.TrackerSweep; csrc/batched_assoc.hip).
+ *
+ *  st_batched_tracker_create_multi: as st_batched_tracker_create, with cfgs[b] = the option set of sequence b
+ *    (`batch` of them).  Whatever st_batched_tracker_create refuses is refused here for ANY member, before any device
+ *    call, and st_last_error() names the member index.  State layout, scratch layout, state_bytes, scratch_bytes and
+ *    get_states are those of section 9.  The option sets are copied; their device copy is owned by the tracker object
+ *    (made by its first launch, freed by st_batched_tracker_destroy).  st_batched_tracker_step on such a tracker
+ *    applies member b's options to sequence b.
+ *
+ *  st_batched_tracker_run: frames [f_begin, f_end) of V recorded videos for every sequence of the tracker (from either
+ *    create function), ONE launch, one wave per sequence: sequence b walks the frames of video video_of[b] and writes
+ *    every frame's rows, ids and count.
+ *      frame_ids (V, F), dets (V, F, max_dets, 8), counts (V, F): the inputs of st_batched_tracker_step per video and
+ *      frame; counts == -1 is a frame the video does not have (ragged lengths, gaps): out_counts = -1, the state does
+ *      not move.  video_of (batch) in [0, V): sequences that share a video read the same rows, nothing is copied.
+ *      out_rows (batch, F, max_dets, 8), out_ids (batch, F, max_dets), out_counts (batch, F): frames outside the range
+ *      are not written.  status (batch): written as st_batched_tracker_step writes it (a code only, never 0).
+ *    DEFINED as equal, on the bits, to f_end - f_begin calls of st_batched_tracker_step whose inputs were gathered
+ *    through video_of - outputs, device state and status.  A capacity overflow is sticky exactly as there: the frame
+ *    and all later ones get count 0 and report the code, until a frame with frame_id 0.  The state persists in
+ *    state_dev between calls, so [0, F) in one call equals [0, k) then [k, F); that also bounds a launch.
+ *    One code of its own: status 3 = video_of[b] outside [0, V) (that sequence reads nothing, counts 0).
+ *    Refused before any launch: null pointers (video_of included), V or F <= 0, a range that is not
+ *    0 <= f_begin < f_end <= F.  Enqueued on `stream`, no host sync.
+ * ---------------------------------------------------------------------- */
+int st_batched_tracker_create_multi(const StTrackerConfig* cfgs, int batch, int max_tracks, int max_dets,
+                                    StBatchedTracker** out);
+int st_batched_tracker_run(StBatchedTracker* t, const int32_t* frame_ids_dev, const float* dets_dev,
+                           const int32_t* counts_dev, const int32_t* video_of_dev, int V, int F, int f_begin, int f_end,
+                           void* state_dev, void* scratch_dev, float* out_rows_dev, int64_t* out_ids_dev,
+                           int32_t* out_counts_dev, int32_t* status_dev, st_stream_t stream);
+
+/* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call
  * (mmtrack/datasets/transforms/loading_disparity.py:74-75 uint16 disparity, :213-215 uint16 depth; mmcv's

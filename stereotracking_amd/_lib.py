@@ -290,6 +290,8 @@ _PROTOS = {
     'st_batched_tracker_get_states': (_i, [_vp, _vp, _i, _vp, _i, _i, C.POINTER(_i), C.POINTER(C.c_longlong),
                                            C.POINTER(_i), _vp]),
     'st_batched_tracker_create': (_i, [C.POINTER(StTrackerConfig), _i, _i, _i, C.POINTER(_vp)]),
+    'st_batched_tracker_create_multi': (_i, [C.POINTER(StTrackerConfig), _i, _i, _i, C.POINTER(_vp)]),
+    'st_batched_tracker_run': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'st_batched_tracker_destroy': (_i, [_vp]),
     'st_batched_tracker_state_bytes': (_sz, [_vp]),
     'st_batched_tracker_scratch_bytes': (_sz, [_vp]),

@@ -20,11 +20,17 @@
 // tracks x detections cost matrix, the Kalman updates per matched track) run across the 64 lanes, the branchy
 // bookkeeping and the Jonker-Volgenant path search run on lane 0 with their working set in LDS / L2, and the chip runs
 // thousands of such waves at once.  State lives in device memory between steps (no per-frame host round trip).
+//
+// Tracker-option sweeps (include/stereotrack.h section 20): the step of one sequence and frame is the device routine
+// assoc_frame; assoc_step_kernel calls it once, assoc_run_kernel walks a whole recorded detection stream with it - one
+// launch per run, the sequence's own option set read from device memory, the detections of a video shared by every
+// sequence that tracks it.  Same routine, same state, same order of operations: a run equals its steps on the bits.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <memory>
+#include <vector>
 
 #include "st_common.h"
 
@@ -595,51 +601,50 @@ __device__ void assign_stage(const Cfg& cfg, DTrack* tracks, const int* tidx, in
 }
 
 // status codes written per sequence
-constexpr int kOk = 0, kTrackOverflow = 1, kDetOverflow = 2;
+constexpr int kOk = 0, kTrackOverflow = 1, kDetOverflow = 2, kBadVideo = 3;
 
-__global__ __launch_bounds__(64) void assoc_step_kernel(Cfg cfg, const int* __restrict__ frame_ids,
-                                                        const float* __restrict__ dets_all,
-                                                        const int* __restrict__ counts, char* state_all,
-                                                        size_t state_stride, char* scratch_all, size_t scratch_stride,
-                                                        float* __restrict__ out_rows, long long* __restrict__ out_ids,
-                                                        int* __restrict__ out_n, int* __restrict__ status,
-                                                        int lap_in_lds) {
-  const int b = blockIdx.x, lane = threadIdx.x;
+// The assignment's working arrays (37 B per row / column of the extended matrix) in the block's dynamic LDS instead of
+// the sequence's slice of the global scratch.  In place, called by the kernels under `if (lap_in_lds)`: as a routine that
+// RETURNS the scratch, the step kernel's dense-sequence time rose by 3 %.
+__device__ __forceinline__ void assignment_arrays_in_lds(Scratch& s, int T, int M) {
+  extern __shared__ double ba_dyn[];
+  const size_t n = (size_t)T + M;
+  char* base = reinterpret_cast<char*>(ba_dyn);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { char* q = base + o; o += align8(bytes); return q; };
+  s.v = (double*)take(sizeof(double) * n);
+  s.d = (double*)take(sizeof(double) * n);
+  s.row_to_col = (int*)take(sizeof(int) * n);
+  s.col_to_row = (int*)take(sizeof(int) * n);
+  s.free_rows = (int*)take(sizeof(int) * n);
+  s.pred = (int*)take(sizeof(int) * n);
+  s.cols = (int*)take(sizeof(int) * n);
+  s.once = take(n);
+}
+
+// ONE frame of ONE sequence, by the sequence's wave: frame `frame_id` with the n detection rows `dets` -> the output
+// rows / ids / count and the sequence's status.  Called once by assoc_step_kernel and once per frame by
+// assoc_run_kernel.  Every exit is uniform across the wave (so is every __syncthreads()); a caller that goes on to
+// another frame puts a barrier behind the call: it orders sh[], lap_ctl, the assignment's arrays and the state in
+// global memory that lanes wrote here for the lanes that read them in the next frame.  cfg and s come by value: by
+// reference the compiler keeps the scratch pointers in private memory (184 B of it against the 12 B the step kernel had).
+// The step kernel's code is sensitive to this signature (scalar-register spills move): DESIGN.md 20 has the timings.
+__device__ __forceinline__ void assoc_frame(const Cfg cfg, Scratch s, SeqHeader* hdr, DTrack* tracks, int frame_id,
+                                            int n, const float* __restrict__ dets, float* __restrict__ orow,
+                                            long long* __restrict__ oid, int* __restrict__ out_n,
+                                            int* __restrict__ status, int lane) {
   const int T = cfg.max_tracks, M = cfg.max_dets;
-  SeqHeader* hdr = reinterpret_cast<SeqHeader*>(state_all + (size_t)b * state_stride);
-  DTrack* tracks = reinterpret_cast<DTrack*>(reinterpret_cast<char*>(hdr) + sizeof(SeqHeader));
-  Scratch s = carve(scratch_all + (size_t)b * scratch_stride, T, M);
-  if (lap_in_lds) {   // the assignment's working arrays (37 B per row / column of the extended matrix) in LDS
-    extern __shared__ double ba_dyn[];
-    const size_t n = (size_t)T + M;
-    char* base = reinterpret_cast<char*>(ba_dyn);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* q = base + o; o += align8(bytes); return q; };
-    s.v = (double*)take(sizeof(double) * n);
-    s.d = (double*)take(sizeof(double) * n);
-    s.row_to_col = (int*)take(sizeof(int) * n);
-    s.col_to_row = (int*)take(sizeof(int) * n);
-    s.free_rows = (int*)take(sizeof(int) * n);
-    s.pred = (int*)take(sizeof(int) * n);
-    s.cols = (int*)take(sizeof(int) * n);
-    s.once = take(n);
-  }
-  const float* dets = dets_all + (size_t)b * M * 8;
-  const int frame_id = frame_ids[b];
-  const int n = counts[b];
-  float* orow = out_rows + (size_t)b * M * 8;
-  long long* oid = out_ids + (size_t)b * M;
   __shared__ int sh[12];   // n_tracks, n_order, n_cand, n_conf, n_tent, n_lost, n_matched, first_stage flag, status
   if (n < 0) {             // padding slot: this sequence has no frame in this step
-    if (lane == 0) out_n[b] = -1;
+    if (lane == 0) *out_n = -1;
     return;
   }
   if (frame_id != 0 && hdr->poisoned != kOk) {   // an earlier step overflowed: the state is not a tracker state any more
-    if (lane == 0) { out_n[b] = 0; status[b] = hdr->poisoned; }
+    if (lane == 0) { *out_n = 0; *status = hdr->poisoned; }
     return;
   }
   if (n > M) {
-    if (lane == 0) { out_n[b] = 0; status[b] = kDetOverflow; hdr->poisoned = kDetOverflow; }
+    if (lane == 0) { *out_n = 0; *status = kDetOverflow; hdr->poisoned = kDetOverflow; }
     return;
   }
   if (lane == 0) {
@@ -754,7 +759,7 @@ __global__ __launch_bounds__(64) void assoc_step_kernel(Cfg cfg, const int* __re
   }
   __syncthreads();
   if (sh[8] != kOk) {
-    if (lane == 0) { status[b] = sh[8]; out_n[b] = 0; hdr->poisoned = sh[8]; }
+    if (lane == 0) { *status = sh[8]; *out_n = 0; hdr->poisoned = sh[8]; }
     return;
   }
   for (int i = lane; i < sh[1]; i += 64) {
@@ -777,7 +782,7 @@ __global__ __launch_bounds__(64) void assoc_step_kernel(Cfg cfg, const int* __re
       if (!drop) ++w;
     }
     hdr->n_tracks = w;
-    out_n[b] = sh[1];
+    *out_n = sh[1];
   }
   __syncthreads();
   {
@@ -795,6 +800,65 @@ __global__ __launch_bounds__(64) void assoc_step_kernel(Cfg cfg, const int* __re
   }
 }
 
+
+__global__ __launch_bounds__(64) void assoc_step_kernel(Cfg cfg, const int* __restrict__ frame_ids,
+                                                        const float* __restrict__ dets_all,
+                                                        const int* __restrict__ counts, char* state_all,
+                                                        size_t state_stride, char* scratch_all, size_t scratch_stride,
+                                                        float* __restrict__ out_rows, long long* __restrict__ out_ids,
+                                                        int* __restrict__ out_n, int* __restrict__ status,
+                                                        int lap_in_lds) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int T = cfg.max_tracks, M = cfg.max_dets;
+  SeqHeader* hdr = reinterpret_cast<SeqHeader*>(state_all + (size_t)b * state_stride);
+  DTrack* tracks = reinterpret_cast<DTrack*>(reinterpret_cast<char*>(hdr) + sizeof(SeqHeader));
+  Scratch s = carve(scratch_all + (size_t)b * scratch_stride, T, M);
+  if (lap_in_lds) assignment_arrays_in_lds(s, T, M);
+  assoc_frame(cfg, s, hdr, tracks, frame_ids[b], counts[b], dets_all + (size_t)b * M * 8, out_rows + (size_t)b * M * 8,
+              out_ids + (size_t)b * M, out_n + b, status + b, lane);
+}
+
+// A whole recorded detection stream in ONE launch: the wave of sequence b walks frames [f_begin, f_end) of video
+// video_of[b] (null: video b) and writes every frame's rows / ids / count.  Equal on the bits to f_end - f_begin launches
+// of assoc_step_kernel on inputs gathered through video_of: the same routine on the same state, which lives in global
+// memory between frames as it does between steps.  cfgs (null: `cfg` for every sequence) = the sequences' own option
+// sets, read once per wave; the capacities are the tracker's.  Sequences that share a video read the same rows.
+__global__ __launch_bounds__(64) void assoc_run_kernel(Cfg cfg, const Cfg* __restrict__ cfgs,
+                                                       const int* __restrict__ frame_ids,
+                                                       const float* __restrict__ dets_all,
+                                                       const int* __restrict__ counts,
+                                                       const int* __restrict__ video_of, int V, int F, int f_begin,
+                                                       int f_end, char* state_all, size_t state_stride,
+                                                       char* scratch_all, size_t scratch_stride,
+                                                       float* __restrict__ out_rows, long long* __restrict__ out_ids,
+                                                       int* __restrict__ out_n, int* __restrict__ status,
+                                                       int lap_in_lds) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int T = cfg.max_tracks, M = cfg.max_dets;
+  if (cfgs) {
+    cfg = cfgs[b];
+    cfg.max_tracks = T; cfg.max_dets = M;
+  }
+  const int v = video_of ? video_of[b] : b;
+  if (v < 0 || v >= V) {   // nothing of this sequence is read or advanced
+    if (lane == 0) {
+      status[b] = kBadVideo;
+      for (int f = f_begin; f < f_end; ++f) out_n[(size_t)b * F + f] = 0;
+    }
+    return;
+  }
+  SeqHeader* hdr = reinterpret_cast<SeqHeader*>(state_all + (size_t)b * state_stride);
+  DTrack* tracks = reinterpret_cast<DTrack*>(reinterpret_cast<char*>(hdr) + sizeof(SeqHeader));
+  Scratch s = carve(scratch_all + (size_t)b * scratch_stride, T, M);
+  if (lap_in_lds) assignment_arrays_in_lds(s, T, M);
+  for (int f = f_begin; f < f_end; ++f) {
+    const size_t in = (size_t)v * F + f, on = (size_t)b * F + f;
+    assoc_frame(cfg, s, hdr, tracks, frame_ids[in], counts[in], dets_all + in * M * 8, out_rows + on * M * 8,
+                out_ids + on * M, out_n + on, status + b, lane);
+    __syncthreads();   // the frame's writes (LDS, scratch, state) before the next frame's reads
+  }
+}
+
 }  // namespace ba
 }  // namespace st
 
@@ -804,8 +868,65 @@ struct StBatchedTracker {
   int batch;
   size_t state_stride, scratch_stride;
   size_t lap_lds_bytes;   // dynamic LDS for the assignment's working arrays; 0 = they stay in the L2-resident scratch
-  int lds_set;
+  int lds_set, lds_set_run;
+  // per-sequence option sets (st_batched_tracker_create_multi; empty otherwise) and their device copy, which the
+  // first launch makes: creating a tracker touches no device
+  std::vector<st::ba::Cfg> cfgs_host;
+  st::ba::Cfg* cfgs_dev;
 };
+
+namespace {
+
+// the tracker object of either create function; `cfg` has passed the checks
+std::unique_ptr<StBatchedTracker> new_batched_tracker(const StTrackerConfig* cfg, int batch, int max_tracks, int max_dets) {
+  using namespace st;
+  auto t = std::make_unique<StBatchedTracker>();
+  t->cfg = ba::Cfg{cfg->obj_score_thr, cfg->init_track_thr, cfg->match_iou_thr, cfg->vel_consist_weight,
+                   cfg->weight_iou_with_det_scores, cfg->num_tentatives, cfg->vel_delta_t, cfg->num_frames_retain,
+                   max_tracks, max_dets};
+  t->batch = batch;
+  t->state_stride = ba::align8(sizeof(ba::SeqHeader) + sizeof(ba::DTrack) * (size_t)max_tracks);
+  t->scratch_stride = ba::scratch_bytes(max_tracks, max_dets);
+  const size_t n = (size_t)max_tracks + max_dets;
+  const size_t need = 2 * ba::align8(sizeof(double) * n) + 5 * ba::align8(sizeof(int) * n) + ba::align8(n);
+  t->lap_lds_bytes = need <= 64 * 1024 ? need : 0;
+  t->lds_set = t->lds_set_run = 0;
+  t->cfgs_dev = nullptr;
+  return t;
+}
+
+bool options_in_range(const StTrackerConfig* cfg) {
+  return cfg->vel_delta_t >= 0 && cfg->vel_delta_t + 1 <= st::ba::WINCAP && cfg->num_tentatives >= 1 &&
+         cfg->num_frames_retain >= 1;
+}
+
+int launch_run(StBatchedTracker* t, const int32_t* frame_ids_dev, const float* dets_dev, const int32_t* counts_dev,
+               const int32_t* video_of_dev, int V, int F, int f_begin, int f_end, void* state_dev, void* scratch_dev,
+               float* out_rows_dev, int64_t* out_ids_dev, int32_t* out_counts_dev, int32_t* status_dev,
+               st_stream_t stream) {
+  using namespace st;
+  if (!t->cfgs_host.empty() && !t->cfgs_dev) {
+    const size_t bytes = sizeof(ba::Cfg) * t->cfgs_host.size();
+    ba::Cfg* p = nullptr;
+    ST_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&p), bytes));
+    const hipError_t e = hipMemcpy(p, t->cfgs_host.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      ST_CHECK_HIP(e);
+    }
+    t->cfgs_dev = p;
+  }
+  ST_ENSURE_DYNAMIC_LDS(ba::assoc_run_kernel, t->lap_lds_bytes, t->lds_set_run);
+  hipLaunchKernelGGL(ba::assoc_run_kernel, dim3(t->batch), dim3(64), t->lap_lds_bytes,
+                     static_cast<hipStream_t>(stream), t->cfg, t->cfgs_dev, frame_ids_dev, dets_dev, counts_dev,
+                     video_of_dev, V, F, f_begin, f_end, static_cast<char*>(state_dev), t->state_stride,
+                     static_cast<char*>(scratch_dev), t->scratch_stride, out_rows_dev,
+                     reinterpret_cast<long long*>(out_ids_dev), out_counts_dev, status_dev, t->lap_lds_bytes ? 1 : 0);
+  ST_CHECK_HIP(hipGetLastError());
+  return ST_OK;
+}
+
+}  // namespace
 
 extern "C" int st_batched_tracker_create(const StTrackerConfig* cfg, int batch, int max_tracks, int max_dets,
                                          StBatchedTracker** out) {
@@ -814,29 +935,35 @@ extern "C" int st_batched_tracker_create(const StTrackerConfig* cfg, int batch, 
   ST_REQUIRE(cfg->struct_size == (int)sizeof(StTrackerConfig), "st_batched_tracker_create: struct_size mismatch");
   ST_REQUIRE(batch > 0 && max_tracks > 0 && max_dets > 0 && max_tracks + max_dets < (1 << 15),
              "st_batched_tracker_create: bad batch / capacities");
-  ST_REQUIRE(cfg->vel_delta_t >= 0 && cfg->vel_delta_t + 1 <= ba::WINCAP && cfg->num_tentatives >= 1 &&
-                 cfg->num_frames_retain >= 1,
-             "st_batched_tracker_create: vel_delta_t must be in [0, %d]", ba::WINCAP - 1);
-  auto t = std::make_unique<StBatchedTracker>();
-  t->cfg.obj_score_thr = cfg->obj_score_thr; t->cfg.init_track_thr = cfg->init_track_thr;
-  t->cfg.match_iou_thr = cfg->match_iou_thr; t->cfg.vel_consist_weight = cfg->vel_consist_weight;
-  t->cfg.weight_iou_with_det_scores = cfg->weight_iou_with_det_scores; t->cfg.num_tentatives = cfg->num_tentatives;
-  t->cfg.vel_delta_t = cfg->vel_delta_t; t->cfg.num_frames_retain = cfg->num_frames_retain;
-  t->cfg.max_tracks = max_tracks; t->cfg.max_dets = max_dets;
-  t->batch = batch;
-  t->state_stride = ba::align8(sizeof(ba::SeqHeader) + sizeof(ba::DTrack) * (size_t)max_tracks);
-  t->scratch_stride = ba::scratch_bytes(max_tracks, max_dets);
-  {
-    const size_t n = (size_t)max_tracks + max_dets;
-    const size_t need = 2 * ba::align8(sizeof(double) * n) + 5 * ba::align8(sizeof(int) * n) + ba::align8(n);
-    t->lap_lds_bytes = need <= 64 * 1024 ? need : 0;
-    t->lds_set = 0;
+  ST_REQUIRE(options_in_range(cfg), "st_batched_tracker_create: vel_delta_t must be in [0, %d]", ba::WINCAP - 1);
+  *out = new_batched_tracker(cfg, batch, max_tracks, max_dets).release();
+  return ST_OK;
+}
+
+extern "C" int st_batched_tracker_create_multi(const StTrackerConfig* cfgs, int batch, int max_tracks, int max_dets,
+                                               StBatchedTracker** out) {
+  using namespace st;
+  if (!cfgs || !out) return set_error(ST_ERR_INVALID, "st_batched_tracker_create_multi: null argument");
+  ST_REQUIRE(batch > 0 && max_tracks > 0 && max_dets > 0 && max_tracks + max_dets < (1 << 15),
+             "st_batched_tracker_create_multi: bad batch / capacities");
+  for (int b = 0; b < batch; ++b) {   // every member, before any device call
+    ST_REQUIRE(cfgs[b].struct_size == (int)sizeof(StTrackerConfig),
+               "st_batched_tracker_create_multi: member %d: struct_size mismatch", b);
+    ST_REQUIRE(options_in_range(&cfgs[b]), "st_batched_tracker_create_multi: member %d: vel_delta_t must be in [0, %d]",
+               b, ba::WINCAP - 1);
   }
+  auto t = new_batched_tracker(&cfgs[0], batch, max_tracks, max_dets);
+  t->cfgs_host.resize((size_t)batch);
+  for (int b = 0; b < batch; ++b)
+    t->cfgs_host[b] = ba::Cfg{cfgs[b].obj_score_thr, cfgs[b].init_track_thr, cfgs[b].match_iou_thr, cfgs[b].vel_consist_weight,
+                      cfgs[b].weight_iou_with_det_scores, cfgs[b].num_tentatives, cfgs[b].vel_delta_t,
+                      cfgs[b].num_frames_retain, max_tracks, max_dets};
   *out = t.release();
   return ST_OK;
 }
 
 extern "C" int st_batched_tracker_destroy(StBatchedTracker* t) {
+  if (t && t->cfgs_dev) (void)hipFree(t->cfgs_dev);
   delete t;
   return ST_OK;
 }
@@ -907,6 +1034,9 @@ extern "C" int st_batched_tracker_step(StBatchedTracker* t, const int32_t* frame
   ST_REQUIRE(frame_ids_dev && dets_dev && counts_dev && state_dev && scratch_dev && out_rows_dev && out_ids_dev &&
                  out_counts_dev && status_dev,
              "st_batched_tracker_step: null pointer");
+  if (!t->cfgs_host.empty())   // per-sequence options: the run kernel over one frame, video b = sequence b
+    return launch_run(t, frame_ids_dev, dets_dev, counts_dev, nullptr, t->batch, 1, 0, 1, state_dev, scratch_dev,
+                      out_rows_dev, out_ids_dev, out_counts_dev, status_dev, stream);
   ST_ENSURE_DYNAMIC_LDS(ba::assoc_step_kernel, t->lap_lds_bytes, t->lds_set);
   hipLaunchKernelGGL(ba::assoc_step_kernel, dim3(t->batch), dim3(64), t->lap_lds_bytes,
                      static_cast<hipStream_t>(stream), t->cfg, frame_ids_dev, dets_dev, counts_dev,
@@ -915,4 +1045,21 @@ extern "C" int st_batched_tracker_step(StBatchedTracker* t, const int32_t* frame
                      status_dev, t->lap_lds_bytes ? 1 : 0);
   ST_CHECK_HIP(hipGetLastError());
   return ST_OK;
+}
+
+extern "C" int st_batched_tracker_run(StBatchedTracker* t, const int32_t* frame_ids_dev, const float* dets_dev,
+                                      const int32_t* counts_dev, const int32_t* video_of_dev, int V, int F, int f_begin,
+                                      int f_end, void* state_dev, void* scratch_dev, float* out_rows_dev,
+                                      int64_t* out_ids_dev, int32_t* out_counts_dev, int32_t* status_dev,
+                                      st_stream_t stream) {
+  using namespace st;
+  if (!t) return set_error(ST_ERR_INVALID, "st_batched_tracker_run: null tracker");
+  ST_REQUIRE(frame_ids_dev && dets_dev && counts_dev && video_of_dev && state_dev && scratch_dev && out_rows_dev &&
+                 out_ids_dev && out_counts_dev && status_dev,
+             "st_batched_tracker_run: null pointer");
+  ST_REQUIRE(V > 0 && F > 0, "st_batched_tracker_run: %d videos x %d frames", V, F);
+  ST_REQUIRE(f_begin >= 0 && f_begin < f_end && f_end <= F, "st_batched_tracker_run: bad frame range [%d, %d) of %d frames",
+             f_begin, f_end, F);
+  return launch_run(t, frame_ids_dev, dets_dev, counts_dev, video_of_dev, V, F, f_begin, f_end, state_dev, scratch_dev,
+                    out_rows_dev, out_ids_dev, out_counts_dev, status_dev, stream);
 }

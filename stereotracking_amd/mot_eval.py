@@ -435,6 +435,34 @@ def kitti_keep_masks(sequences, classes, max_occlusion=2, max_truncation=0, min_
     return out
 
 
+def image_space_rows(frames, rows, ids, n):
+    """Tracker outputs on the host - frames (T, B), rows (T, B, M, row floats), ids (T, B, M), n (T, B), views allowed -
+    -> one (R, 6) fp64 array per sequence: (frame, id, x, y, w, h) of every output row, in step order, in IMAGE
+    space: the tracker's rows carry depth-scaled boxes, which are scaled back about their centres by 1 / scale
+    (the row's scale column) with the fp32 operations of mot.scale_bbox, as every product path does before a box is
+    reported or scored.  The ground truth they are scored against is the image-space one MOTDroneMetrics uses.
+    Shared by TrackCollector.prediction_rows and sweep.SweepResult.prediction_rows."""
+    from .records import TRACK_ROW
+    two = np.float32(2.0)
+    T, B = n.shape
+    out = []
+    for b in range(B):
+        parts = []
+        for t in range(T):
+            k = int(n[t, b])
+            if k <= 0:
+                continue
+            r = rows[t, b, :k]
+            inv = np.float32(1.0) / r[:, TRACK_ROW.scale]
+            cx, cy = (r[:, 0] + r[:, 2]) / two, (r[:, 1] + r[:, 3]) / two
+            w, h = (r[:, 2] - r[:, 0]) * inv, (r[:, 3] - r[:, 1]) * inv
+            box = np.stack([cx - w / two, cy - h / two, cx + w / two, cy + h / two], 1).astype(np.float64)
+            parts.append(np.column_stack([np.full(k, frames[t, b], np.float64), ids[t, b, :k].astype(np.float64),
+                                          box[:, 0], box[:, 1], box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]]))
+        out.append(np.concatenate(parts) if parts else np.zeros((0, 6)))
+    return out
+
+
 class TrackCollector:
     """Collects the per-step outputs of a BatchedGpuTracker run on the device and brings them to the host with ONE
     device-to-host copy per run (to_host), not one per step."""
@@ -460,30 +488,8 @@ class TrackCollector:
                 flat[:a].view(np.int64).reshape(tuple(ids.shape)), flat[b:].view(np.int32).reshape(tuple(n.shape)))
 
     def prediction_rows(self):
-        """One (R, 6) fp64 array per sequence: (frame, id, x, y, w, h) of every output row, in step order, in IMAGE
-        space: the tracker's rows carry depth-scaled boxes, which are scaled back about their centres by 1 / scale
-        (the row's scale column) with the fp32 operations of mot.scale_bbox, as every product path does before a box is
-        reported or scored.  The ground truth they are scored against is the image-space one MOTDroneMetrics uses."""
-        from .records import TRACK_ROW
-        two = np.float32(2.0)
-        frames, rows, ids, n = self.to_host()
-        T, B = n.shape
-        out = []
-        for b in range(B):
-            parts = []
-            for t in range(T):
-                k = int(n[t, b])
-                if k <= 0:
-                    continue
-                r = rows[t, b, :k]
-                inv = np.float32(1.0) / r[:, TRACK_ROW.scale]
-                cx, cy = (r[:, 0] + r[:, 2]) / two, (r[:, 1] + r[:, 3]) / two
-                w, h = (r[:, 2] - r[:, 0]) * inv, (r[:, 3] - r[:, 1]) * inv
-                box = np.stack([cx - w / two, cy - h / two, cx + w / two, cy + h / two], 1).astype(np.float64)
-                parts.append(np.column_stack([np.full(k, frames[t, b], np.float64), ids[t, b, :k].astype(np.float64),
-                                              box[:, 0], box[:, 1], box[:, 2] - box[:, 0], box[:, 3] - box[:, 1]]))
-            out.append(np.concatenate(parts) if parts else np.zeros((0, 6)))
-        return out
+        """One (R, 6) fp64 array per sequence: image_space_rows of the run (to_host)."""
+        return image_space_rows(*self.to_host())
 
 
 def evaluate_sweep(predictions, gt, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None, backend='device',

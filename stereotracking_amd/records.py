@@ -18,6 +18,7 @@ from .structures import InstanceData
 
 BOX, SCORE, LABEL = slice(0, 4), 4, 5                  # the first six columns of every row layout above
 REC_HEADER, REC_COUNT, REC_CAP = 0, 0, 1               # frame record: the header row and its first two columns
+REC_VALID = 2                                          # header row: the valid-frame flag (0 = batch padding, not a frame)
 REC_FLOATS, REC_FLOATS_BOTH = 8, 13
 REC_DEPTH, REC_SCALE, REC_SCALED_BOX, REC_PRIOR = 6, 7, slice(8, 12), 12
 TrackLayout = namedtuple('TrackLayout', 'floats depth scale gt_depth')
