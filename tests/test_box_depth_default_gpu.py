@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import guard_memory as gm
 import box_depth_cases as B
 import depth_methods_ref as R
 
@@ -25,12 +26,12 @@ def run_default(case, cuda, maps=None, is_depth=None, via_method=False):
     is_depth = case.is_depth if is_depth is None else is_depth
     N, Cc, H, W = maps.shape
     M = case.boxes.shape[1]
-    dev_map = torch.from_numpy(maps.copy()).to(cuda)
-    boxes = torch.from_numpy(case.boxes.copy()).to(cuda)
-    counts = torch.from_numpy(case.counts.copy()).to(cuda)
-    d = torch.full((N, M), 7.0, device=cuda)                  # poisoned: every row must be written
-    s = torch.full((N, M), 7.0, device=cuda)
-    b = torch.full((N, M, 4), 7.0, device=cuda)
+    dev_map = gm.device_planes(maps.copy(), cuda)            # channel 0 is the map: the others are never read
+    boxes = gm.device_input(case.boxes.copy(), cuda)
+    counts = gm.device_input(case.counts.copy(), cuda)
+    d = gm.device_output((N, M), cuda, 7.0)                   # poisoned: every row must be written
+    s = gm.device_output((N, M), cuda, 7.0)
+    b = gm.device_output((N, M, 4), cuda, 7.0)
     base = (-1.0, 1.0) if is_depth else (0.25, 640.0)
     args = (ptr(dev_map), Cc * H * W, N, H, W, ptr(boxes), ptr(counts), M, *base, None, 0, current_stream(), ptr(d),
             ptr(s), ptr(b))
@@ -108,3 +109,14 @@ def test_disparity_and_gt_depth_input_agree(builder, cuda):
     assert np.array_equal(from_disp[0] == -1, from_depth[0] == -1)
     assert np.array_equal(np.isnan(from_disp[0]), np.isnan(from_depth[0]))
     assert (from_disp[0] > 0).any()
+
+
+GUARDED = [test_default_estimator_matches_the_restatement, test_method_zero_is_the_default_kernel]
+NAN_BY_CONTRACT = GUARDED                                   # a NaN depth is one of the estimator's decisions
+
+
+# ---- the same entry points over hostile surroundings (tests/guard_memory.py) -------------------------------------------
+test_entry_points_are_blind_to_guard_bands = gm.guarded_test(GUARDED, NAN_BY_CONTRACT, doc="""st_box_depth twice on every crafted case (guard_memory.run_both): as it stands, and with the disparity map
+    between guard bands of 0xFF bytes and NaN in its planes 1 and 2 (windows that wrap, clamp or touch the last row must
+    not leave channel 0).  The hostile run passes the 1-ulp bar against the restatement and equals the friendly run bit
+    for bit; bands, maps, boxes and counts are unchanged bytewise.""")

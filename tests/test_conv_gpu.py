@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import guard_memory
 from stereotracking_amd import _lib
 from stereotracking_amd._lib import StConvDesc, check, ptr
 
@@ -31,7 +32,10 @@ def pack(w, bias=None, bn=None, eps=1e-3):
 
 def run_conv(x_nchw, w, bias, stride, pad, act, dev, variant=-1, res=None, post_scale=1.0, split=None, up=False,
              in_ld=None, in_off=0):
+    """Buffers come from the ambient guard_memory session: finite garbage in the unused channels and plain allocations,
+    unless a guard test (guard_memory.run_both) says otherwise."""
     lib = _lib.load()
+    mem = guard_memory.current()
     N, Cin, Hi, Wi = x_nchw.shape
     Cout, _, KH, KW = w.shape
     Ho = (Hi + 2 * pad - KH) // stride + 1
@@ -39,7 +43,7 @@ def run_conv(x_nchw, w, bias, stride, pad, act, dev, variant=-1, res=None, post_
     in_ld = in_ld or Cin
     xin = torch.randn(N, Hi, Wi, in_ld) * 3.0  # garbage in the unused channels
     xin[..., in_off:in_off + Cin] = x_nchw.permute(0, 2, 3, 1)
-    xin = xin.contiguous().to(dev)
+    xin = mem.input(xin, dev, in_off, Cin)
     wp, bp = pack(w, bias)
     wp, bp = wp.to(dev), bp.to(dev)
     d = StConvDesc()
@@ -54,19 +58,19 @@ def run_conv(x_nchw, w, bias, stride, pad, act, dev, variant=-1, res=None, post_
         wino = wino.to(dev)
         d.wgt_wino_dev = wino.data_ptr()
     s = Cout if split is None else split
-    out1 = torch.full((N, Ho, Wo, s + 4), -777.0, device=dev)  # ld = s+4, off = 4
+    out1 = mem.output((N, Ho, Wo, s + 4), dev)  # ld = s+4, off = 4; filled with -777
     d.out1_dev = out1.data_ptr(); d.out1_ld, d.out1_off, d.split = s + 4, 4, s
     out2 = None
     if split is not None:
-        out2 = torch.full((N, Ho, Wo, Cout - s), -777.0, device=dev)
+        out2 = mem.output((N, Ho, Wo, Cout - s), dev)
         d.out2_dev = out2.data_ptr(); d.out2_ld, d.out2_off = Cout - s, 0
     upb = None
     if up:
-        upb = torch.full((N, 2 * Ho, 2 * Wo, Cout), -777.0, device=dev)
+        upb = mem.output((N, 2 * Ho, 2 * Wo, Cout), dev)
         d.up_dev = upb.data_ptr(); d.up_ld, d.up_off = Cout, 0
     resb = None
     if res is not None:
-        resb = res.permute(0, 2, 3, 1).contiguous().to(dev)
+        resb = mem.input(res.permute(0, 2, 3, 1), dev)
         d.res_dev = resb.data_ptr(); d.res_ld, d.res_off = Cout, 0
     d.post_scale = post_scale
     d.act = act
@@ -183,14 +187,21 @@ def test_conv_upsampled_store_coordinates(shape, cuda):                      # l
         assert torch.equal(up, F.interpolate(got, scale_factor=2, mode='nearest'))
 
 
-@pytest.mark.parametrize('variant', [12, 13, 15, 18])
+LDS_DMA_TILE_COUT = {12: 128, 13: 64, 15: 32, 18: 64}      # LDS-DMA tile variant -> the cout extent of its tile
+
+
+def lds_dma_tile_divides(variant, cout):
+    """The tile's cout extent must divide the padded Cout (conv_variant_valid of csrc/conv_igemm.hip)."""
+    return ((cout + 31) // 32 * 32) % LDS_DMA_TILE_COUT[variant] == 0
+
+
+@pytest.mark.parametrize('variant', sorted(LDS_DMA_TILE_COUT))
 @pytest.mark.parametrize('case', [(2, 12, 20, 36, 128, 3, 1), (1, 32, 23, 41, 64, 3, 2), (1, 24, 10, 12, 64, 3, 2),
                                   (2, 64, 7, 9, 192, 1, 1)])
 def test_conv_lds_dma_variants_zero_fill_and_ragged(variant, case, cuda):
     """LDS-DMA staging: padding taps, ragged M tiles and the K tail must read as zeros."""
     N, Cin, H, W, Cout, k, stride = case
-    bn = {12: 128, 13: 64, 15: 32, 18: 64}[variant]
-    if ((Cout + 31) // 32 * 32) % bn:
+    if not lds_dma_tile_divides(variant, Cout):
         pytest.skip('tile does not divide Cout')
     torch.manual_seed(variant + sum(case))
     x = torch.randn(N, Cin, H, W) + 3.0  # non-zero mean: a missed zero fill shows up at the borders
@@ -244,18 +255,22 @@ def test_spp_pool_matches_torch_maxpool(N, H, W, Cc, cuda):
     lib = _lib.load()
     torch.manual_seed(H)
     x = torch.randn(N, Cc, H, W)
+    mem = guard_memory.current()
     cat = torch.full((N, H, W, 4 * Cc + 8), -5.0)
     cat[..., 8:8 + Cc] = x.permute(0, 2, 3, 1)
-    cat = cat.to(cuda)
+    # a max reduction drops a NaN: under a guard test the buffer stands between +Inf images and +Inf is among the slack
+    cat = mem.framed(cat, cuda, 8, 4 * Cc, written=True)
+    before = cat.cpu()
+    assert mem.garbage == 'nonfinite' or torch.all(before[..., :8] == -5.0)
     check(lib.st_spp_pool(ptr(cat), 4 * Cc + 8, 8, N, H, W, Cc, ptr(cat), 4 * Cc + 8, 8, _lib.current_stream()))
     torch.cuda.synchronize()
     got = cat.cpu()
-    assert torch.all(got[..., :8] == -5.0)
+    assert guard_memory.same_bits(got[..., :8], before[..., :8]), 'wrote outside its channel slice'
     ref = torch.cat([x] + [F.max_pool2d(x, k, 1, k // 2) for k in (5, 9, 13)], 1).permute(0, 2, 3, 1)
     assert torch.equal(got[..., 8:], ref)
     # separate input buffer (x is copied into the first C channels of out)
-    xin = x.permute(0, 2, 3, 1).contiguous().to(cuda)
-    out = torch.empty(N, H, W, 4 * Cc, device=cuda)
+    xin = mem.framed(x.permute(0, 2, 3, 1), cuda)
+    out = mem.output((N, H, W, 4 * Cc), cuda)
     check(lib.st_spp_pool(ptr(xin), Cc, 0, N, H, W, Cc, ptr(out), 4 * Cc, 0, _lib.current_stream()))
     torch.cuda.synchronize()
     assert torch.equal(out.cpu(), ref)
@@ -283,9 +298,13 @@ def test_fused_focus_stem_matches_torch(N, H, W, cout, act, planes, cuda):
     bp = torch.empty((cout + 31) // 32 * 32, dtype=torch.float32)
     check(lib.st_stem_pack_weights(ptr(w), None, ptr(gamma), ptr(beta), ptr(mean), ptr(var), eps, cout, planes,
                                    ptr(wp), ptr(bp)))
-    xd, wd, bd = x.to(cuda), wp.to(cuda), bp.to(cuda)
+    mem = guard_memory.current()
+    xh = x.clone()
+    if planes == 1 and mem.garbage == 'nonfinite':
+        xh[:, 1:] = float('nan')                                       # "never read"
+    xd, wd, bd = mem.input(xh, cuda), wp.to(cuda), bp.to(cuda)
     ld, off = cout + 8, 4
-    out = torch.full((N, H // 2, W // 2, ld), -777.0, device=cuda)
+    out = mem.output((N, H // 2, W // 2, ld), cuda)
     check(lib.st_stem_focus_conv(ptr(xd), N, H, W, planes, ptr(wd), ptr(bd), cout, ptr(out), ld, off, act, None))
     torch.cuda.synchronize()
     xx = x.double()
@@ -313,7 +332,8 @@ def test_fused_stem_raw_uint8_frames_equal_pack_then_stem(N, h, w, H, W, cout, p
     import ctypes as C
     lib = _lib.load()
     torch.manual_seed(3)
-    frames = [torch.randint(0, 256, (3, h, w), dtype=torch.uint8).to(cuda) for _ in range(N)]
+    mem = guard_memory.current()
+    frames = [mem.input(torch.randint(0, 256, (3, h, w), dtype=torch.uint8), cuda) for _ in range(N)]
     wgt = torch.randn(cout, 12, 3, 3) / 200.0
     gamma, beta, mean, var = torch.rand(cout) + 0.5, torch.randn(cout) * 0.2, torch.randn(cout) * 0.5, torch.rand(cout) + 0.5
     wp = torch.empty(lib.st_stem_packed_floats(cout), dtype=torch.float32)
@@ -328,7 +348,7 @@ def test_fused_stem_raw_uint8_frames_equal_pack_then_stem(N, h, w, H, W, cout, p
     x = torch.empty(N, 3, H, W, device=cuda)
     check(lib.st_pack_raw_frames(table, N, h, w, H, W, pad, ptr(x), None))
     ref = torch.full((N, H // 2, W // 2, cout), -7.0, device=cuda)
-    got = torch.full((N, H // 2, W // 2, cout), -7.0, device=cuda)
+    got = mem.output((N, H // 2, W // 2, cout), cuda, fill=-7.0)
     check(lib.st_stem_focus_conv(ptr(x), N, H, W, 3, ptr(wd), ptr(bd), cout, ptr(ref), cout, 0, 1, None))
     check(lib.st_stem_focus_conv_u8(table, N, h, w, H, W, pad, ptr(wd), ptr(bd), cout, ptr(got), cout, 0, 1, None))
     torch.cuda.synchronize()
@@ -398,12 +418,13 @@ def test_chained_pointwise_pair_matches_torch(cin, N, H, W, cuda):
     x = torch.randn(N, cin, H, W)
     wa, ba = torch.randn(64, cin, 1, 1) / cin ** 0.5, torch.randn(64)
     wb, bb = torch.randn(32, 32, 1, 1) / 32 ** 0.5, torch.randn(32)
-    xin = x.permute(0, 2, 3, 1).contiguous().to(cuda)
+    mem = guard_memory.current()
+    xin = mem.input(x.permute(0, 2, 3, 1), cuda)
     (wpa, bpa), (wpb, bpb) = pack(wa, ba), pack(wb, bb)
     wpa, bpa, wpb, bpb = wpa.to(cuda), bpa.to(cuda), wpb.to(cuda), bpb.to(cuda)
-    main = torch.full((N, H, W, 32), -777.0, device=cuda)
-    cat = torch.full((N, H, W, 64), -777.0, device=cuda)      # short goes to channels [32, 64)
-    tmp = torch.full((N, H, W, 36), -777.0, device=cuda)      # chained output at channel offset 4
+    main = mem.output((N, H, W, 32), cuda)
+    cat = mem.output((N, H, W, 64), cuda)      # short goes to channels [32, 64)
+    tmp = mem.output((N, H, W, 36), cuda)      # chained output at channel offset 4
     a = StConvDesc()
     a.in_dev = xin.data_ptr(); a.N, a.Hi, a.Wi, a.Cin, a.in_ld, a.in_off = N, H, W, cin, cin, 0
     a.wgt_dev = wpa.data_ptr(); a.bias_dev = bpa.data_ptr()
@@ -555,9 +576,10 @@ def test_fused_stage1_front_matches_separate_convolutions(N, H, W, in_ld, in_off
     wm, bm = torch.randn(64, 64, 1, 1) / 8.0, torch.randn(64) * 0.5
     wc, bc = torch.randn(32, 32, 1, 1) / 32 ** 0.5, torch.randn(32) * 0.5
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    mem = guard_memory.current()
     xin = torch.randn(N, H, W, in_ld) * 3.0
     xin[..., in_off:in_off + 32] = x.permute(0, 2, 3, 1)
-    xin = xin.contiguous().to(cuda)
+    xin = mem.input(xin, cuda, in_off, 32)
     packed = [pack(w3, b3), pack(wm, bm), pack(wc, bc)]
     dev = [(w.to(cuda), b.to(cuda)) for w, b in packed]
     frags = []
@@ -586,8 +608,8 @@ def test_fused_stage1_front_matches_separate_convolutions(N, H, W, in_ld, in_off
         return a, m, c
 
     def bufs():
-        return (torch.full((N, Ho, Wo, 64), -777.0, device=cuda), torch.full((N, Ho, Wo, 32), -777.0, device=cuda),
-                torch.full((N, Ho, Wo, 64), -777.0, device=cuda), torch.full((N, Ho, Wo, 36), -777.0, device=cuda))
+        return (mem.output((N, Ho, Wo, 64), cuda), mem.output((N, Ho, Wo, 32), cuda),
+                mem.output((N, Ho, Wo, 64), cuda), mem.output((N, Ho, Wo, 36), cuda))
 
     s3, main, cat, tmp = bufs()
     a, m, c = descs(s3, main, cat, tmp)
@@ -661,12 +683,13 @@ def test_chained_resident_pointwise_pair_matches_torch(cin, N, H, W, cuda):
     x = torch.randn(N, cin, H, W)
     wa, ba = torch.randn(128, cin, 1, 1) / cin ** 0.5, torch.randn(128)
     wb, bb = torch.randn(64, 64, 1, 1) / 8.0, torch.randn(64)
-    xin = x.permute(0, 2, 3, 1).contiguous().to(cuda)
+    mem = guard_memory.current()
+    xin = mem.input(x.permute(0, 2, 3, 1), cuda)
     (wpa, bpa), (wpb, bpb) = pack(wa, ba), pack(wb, bb)
     wpa, bpa, wpb, bpb = wpa.to(cuda), bpa.to(cuda), wpb.to(cuda), bpb.to(cuda)
-    main = torch.full((N, H, W, 64), -777.0, device=cuda)
-    cat = torch.full((N, H, W, 128), -777.0, device=cuda)     # short goes to channels [64, 128)
-    tmp = torch.full((N, H, W, 68), -777.0, device=cuda)      # chained output at channel offset 4
+    main = mem.output((N, H, W, 64), cuda)
+    cat = mem.output((N, H, W, 128), cuda)     # short goes to channels [64, 128)
+    tmp = mem.output((N, H, W, 68), cuda)      # chained output at channel offset 4
     a = StConvDesc()
     a.in_dev = xin.data_ptr(); a.N, a.Hi, a.Wi, a.Cin, a.in_ld, a.in_off = N, H, W, cin, cin, 0
     a.wgt_dev = wpa.data_ptr(); a.bias_dev = bpa.data_ptr()
@@ -723,8 +746,10 @@ def test_product_library_refuses_the_parked_split_instances(cuda):
 
 # ---- fused tail of a stage-1 CSP branch: bottleneck conv2 (Winograd, + identity) -> final_conv (1x1 on the concat) ----
 def _csp_tail(dev, N, H, W, avg, seed, in_ld=32, in_off=0):
-    """-> (fused output, conv2 of the unfused Winograd launch, final of the unfused launches, fp64 reference), NCHW."""
+    """-> (fused output, conv2 of the unfused Winograd launch, final of the unfused launches, fp64 reference), NCHW.
+    Buffers come from the ambient guard_memory session, as in run_conv."""
     lib = _lib.load()
+    mem = guard_memory.current()
     g = torch.Generator().manual_seed(seed)
     tmp = torch.randn(N, 32, H, W, generator=g)                       # bottleneck conv1 output = conv2 input
     main = torch.randn(N, 32, H, W, generator=g)                      # identity of the bottleneck
@@ -737,11 +762,15 @@ def _csp_tail(dev, N, H, W, avg, seed, in_ld=32, in_off=0):
     nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous()
     xin = torch.randn(N, H, W, in_ld, generator=g) * 3.0
     xin[..., in_off:in_off + 32] = nhwc(tmp)
-    xin = xin.to(dev)
+    xin = mem.input(xin, dev, in_off, 32)
     cat = torch.full((N, H, W, 72), -777.0)                            # concat buffer: ld 72, conv2 -> [4, 36), short -> [36, 68)
     cat[..., 36:68] = nhwc(short)
-    cat = cat.to(dev)
-    mainb, otherb = nhwc(main).to(dev), (nhwc(other).to(dev) if avg else None)
+    if mem.garbage == 'nonfinite':                                     # both sides of final_conv's slice [4, 68)
+        cat[..., :4], cat[..., 68:] = float('nan'), float('inf')
+    cat_host = cat.clone()
+    cat = mem.input(cat, dev)
+    mainb = mem.input(nhwc(main), dev)
+    otherb = mem.input(nhwc(other), dev) if avg else None
     wp2, bp2 = pack(w2, b2)
     wino = torch.empty(lib.st_wino_packed_floats(32, 32), dtype=torch.float32)
     check(lib.st_wino_pack_weights(ptr(wp2), 32, 32, ptr(wino)), 'st_wino_pack_weights')
@@ -749,7 +778,7 @@ def _csp_tail(dev, N, H, W, avg, seed, in_ld=32, in_off=0):
     frag = torch.empty(lib.st_csp_tail_frag_floats(), dtype=torch.float32)
     check(lib.st_csp_tail_pack_frags(ptr(wpf), ptr(frag)), 'st_csp_tail_pack_frags')
     wp2d, bp2d, winod, wpfd, bpfd, fragd = (t.to(dev) for t in (wp2, bp2, wino, wpf, bpf, frag))
-    out = torch.full((N, H, W, 68), -777.0, device=dev)               # ld 68, off 4
+    out = mem.output((N, H, W, 68), dev)               # ld 68, off 4
 
     def descs(cat_t, out_t):
         c2 = StConvDesc()
@@ -775,7 +804,8 @@ def _csp_tail(dev, N, H, W, avg, seed, in_ld=32, in_off=0):
     torch.cuda.synchronize()
     o = out.cpu()
     assert torch.all(o[..., :4] == -777.0), 'kernel wrote outside its channel slice'
-    assert torch.all(cat.cpu()[..., :36] == -777.0), 'the fused launch must not write conv2\'s output tensor'
+    assert torch.all(cat_host[..., 4:36] == -777.0) and guard_memory.same_bits(cat.cpu()[..., :36], cat_host[..., :36]), \
+        'the fused launch must not write conv2\'s output tensor'
     fused = o[..., 4:].permute(0, 3, 1, 2)
     # the two launches it replaces, on buffers of their own
     cat2, out2 = cat.clone(), torch.full_like(out, -777.0)

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import depth_methods_ref as R
+import guard_memory as gm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
@@ -26,9 +27,9 @@ def run_method(disp, boxes, counts, method, baseline=0.25, focal=640.0):
     from stereotracking_amd._lib import check, current_stream, ptr
     N, Cc, H, W = disp.shape
     M = boxes.shape[1]
-    d = torch.full((N, M), 7.0, device=disp.device)          # poisoned: every row must be written
-    s = torch.full((N, M), 7.0, device=disp.device)
-    b = torch.full((N, M, 4), 7.0, device=disp.device)
+    d = gm.device_output((N, M), disp.device, 7.0)           # poisoned: every row must be written
+    s = gm.device_output((N, M), disp.device, 7.0)
+    b = gm.device_output((N, M, 4), disp.device, 7.0)
     check(_lib.load().st_box_depth_method(ptr(disp.contiguous()), Cc * H * W, N, H, W, ptr(boxes.contiguous()),
                                           ptr(counts), M, baseline, focal, None, 0, current_stream(), ptr(d), ptr(s),
                                           ptr(b), CODES[method]), 'st_box_depth_method')
@@ -89,10 +90,9 @@ def _check_maps(disp_np, method, cuda, rng, is_depth=False, M=64, cc=3):
     N, H, W = disp_np.shape
     boxes = np.stack([_boxes(rng, H, W, M) for _ in range(N)])
     counts = np.asarray([M - 3 * i for i in range(N)], np.int32)
-    dev_map = torch.from_numpy(np.repeat(disp_np[:, None], cc, axis=1)).to(cuda)
+    dev_map = gm.device_planes(np.repeat(disp_np[:, None], cc, axis=1), cuda)    # channel 0 is the map
     base = (-1.0, 1.0) if is_depth else (0.25, 640.0)
-    gd, gs, gb = run_method(dev_map, torch.from_numpy(boxes).to(cuda), torch.from_numpy(counts).to(cuda), method,
-                            *base)
+    gd, gs, gb = run_method(dev_map, gm.device_input(boxes, cuda), gm.device_input(counts, cuda), method, *base)
     for n in range(N):
         k = counts[n]
         dmap = disp_np[n] if is_depth else R.depth_map(disp_np[n])
@@ -292,3 +292,13 @@ def test_median_config_builds_and_tracks(airdrone, cuda):
     assert sum(len(s.pred_track_instances) for s in out) > 0
     runner = next(iter(model._dense.values()))[0]
     assert runner.depth_method == 'median' and all(p.depth_method == 'median' for p in runner.pipes)
+
+
+GUARDED = [test_kernel_on_random_maps, test_kernel_in_gt_depth_mode]      # st_box_depth_method, every estimator
+NAN_BY_CONTRACT = GUARDED                                                  # a NaN depth is one of their decisions
+
+
+# ---- the same entry points over hostile surroundings (tests/guard_memory.py) -------------------------------------------
+test_entry_points_are_blind_to_guard_bands = gm.guarded_test(GUARDED, NAN_BY_CONTRACT, doc="""st_box_depth_method twice (guard_memory.run_both): as it stands, and with the map between guard bands of 0xFF
+    bytes and NaN in its planes 1 and 2.  The hostile run passes the test's own bar against the restatement and equals
+    the friendly run bit for bit.""")

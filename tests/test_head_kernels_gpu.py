@@ -14,6 +14,7 @@ import ctypes as C
 import pytest
 import torch
 
+import guard_memory
 from stereotracking_amd import _lib
 from stereotracking_amd._lib import StConvDesc, StHeadPredLevel, check, ptr
 from test_conv_gpu import assert_close, pack, ref_conv
@@ -25,10 +26,12 @@ GUARD = -777.0
 
 class Problem:
     """One 3x3 / stride 1 / pad 1 layer: input as a channel slice of a wider NHWC buffer (garbage around it), output at
-    a channel offset inside a buffer pre-filled with GUARD."""
+    a channel offset inside a buffer pre-filled with GUARD.  Buffers come from the ambient guard_memory session: finite
+    garbage and plain allocations, unless a guard test says otherwise."""
 
     def __init__(self, N, H, W, cin, cout, dev, seed, in_pad=(0, 0), out_pad=(4, 4), res=False):
         lib = _lib.load()
+        self.mem = guard_memory.current()
         g = torch.Generator().manual_seed(seed)
         self.shape = (N, H, W, cin, cout)
         self.x = torch.randn(N, cin, H, W, generator=g) + 0.5
@@ -42,12 +45,13 @@ class Problem:
         wino = torch.empty(lib.st_wino_packed_floats(cout, cin), dtype=torch.float32)
         check(lib.st_wino_pack_weights(ptr(wp), cout, cin, ptr(wino)), 'st_wino_pack_weights')
         self.dev = dev
-        self.xin, self.wp, self.bp, self.wino = xin.contiguous().to(dev), wp.to(dev), bp.to(dev), wino.to(dev)
-        self.res = torch.randn(N, H, W, cout, generator=g).to(dev) if res else None
+        self.xin = self.mem.input(xin, dev, self.in_off, cin)
+        self.wp, self.bp, self.wino = wp.to(dev), bp.to(dev), wino.to(dev)
+        self.res = self.mem.input(torch.randn(N, H, W, cout, generator=g), dev) if res else None
 
     def out_buffer(self):
         N, H, W, _, _ = self.shape
-        return torch.full((N, H, W, self.out_ld), GUARD, device=self.dev)
+        return self.mem.output((N, H, W, self.out_ld), self.dev, GUARD)
 
     def desc(self, out):
         N, H, W, cin, cout = self.shape
@@ -141,10 +145,12 @@ def test_grouped_winograd_launch_refuses_what_it_cannot_run(stlib, cuda):
 # ---- st_head_pred ----------------------------------------------------------------------------------------------------
 class HeadLevel:
     """One level: both tower outputs as channel slices [cls | reg] of ONE wider buffer (ld = 2 feat + 8, the way the plan
-    keeps [cls_feat0 | reg_feat0]), or as two tensors of their own; head rows pre-filled with GUARD, 3 rows past M."""
+    keeps [cls_feat0 | reg_feat0]), or as two tensors of their own; head rows pre-filled with GUARD, 3 rows past M.
+    Buffers come from the ambient guard_memory session, as for Problem."""
 
     def __init__(self, feat, M, dev, seed, shared):
         g = torch.Generator().manual_seed(seed)
+        self.mem = guard_memory.current()
         self.M, self.feat = M, feat
         self.xc = torch.randn(M, feat, generator=g) + 1.5          # non-zero mean: a dropped lane or channel quad shows
         self.xr = torch.randn(M, feat, generator=g) - 1.0
@@ -155,11 +161,12 @@ class HeadLevel:
             ld = 2 * feat + 8
             buf = torch.randn(M, ld, generator=g) * 5.0
             buf[:, 4:4 + feat], buf[:, 4 + feat:4 + 2 * feat] = self.xc, self.xr
-            self.cls = self.reg = buf.to(dev)
+            self.cls = self.reg = self.mem.input(buf, dev, 4, 2 * feat)
             self.cls_ld = self.reg_ld = ld
             self.cls_off, self.reg_off = 4, 4 + feat
         else:
-            self.cls, self.reg = self.xc.contiguous().to(dev), self.xr.contiguous().to(dev)
+            self.cls = self.mem.input(self.xc, dev)
+            self.reg = self.mem.input(self.xr, dev)
             self.cls_ld = self.reg_ld = feat
             self.cls_off = self.reg_off = 0
         (wcp, bcp), (wrp, brp) = pack(self.wc, self.bc), pack(self.wr, self.br)
@@ -167,7 +174,7 @@ class HeadLevel:
         self.dev = dev
 
     def rows(self):
-        return torch.full((self.M + 3, 8), GUARD, device=self.dev)
+        return self.mem.output((self.M + 3, 8), self.dev, GUARD)
 
     def level(self, out):
         return StHeadPredLevel(self.cls.data_ptr(), self.cls_ld, self.cls_off, self.reg.data_ptr(), self.reg_ld,

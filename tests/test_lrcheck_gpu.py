@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import guard_memory as gm
 import lrcheck_ref as R
 from oracle import c_oracle
 from oracle import depth as odepth
@@ -33,8 +34,8 @@ def same(a, b):
 def softargmin_right(V, T, cuda):
     lib = _lib.load()
     N, H, W, D = V.shape
-    v = torch.from_numpy(np.array(V, np.float32)).to(cuda)
-    o = torch.full((N, H, W), float('nan'), device=cuda)
+    v = gm.device_input(np.array(V, np.float32), cuda)
+    o = gm.device_output((N, H, W), cuda, float('nan'))
     check(lib.st_softargmin_right(ptr(v), N, H, W, D, T, ptr(o), current_stream()), 'st_softargmin_right')
     torch.cuda.synchronize()
     return o.cpu().numpy()
@@ -44,9 +45,9 @@ def lr_check_pack(dL, dR, s, valid_hw, lr_max_diff, cuda, want_mask=True):
     lib = _lib.load()
     N, Hl, Wl = dL.shape
     H, W = Hl * s, Wl * s
-    l, r = torch.from_numpy(np.array(dL, np.float32)).to(cuda), torch.from_numpy(np.array(dR, np.float32)).to(cuda)
-    out = torch.full((N, 3, H, W), float('nan'), device=cuda)
-    mask = torch.full((N, 1, H, W), float('nan'), device=cuda) if want_mask else None
+    l, r = gm.device_input(np.array(dL, np.float32), cuda), gm.device_input(np.array(dR, np.float32), cuda)
+    out = gm.device_output((N, 3, H, W), cuda, float('nan'))
+    mask = gm.device_output((N, 1, H, W), cuda, float('nan')) if want_mask else None
     check(lib.st_lr_check_pack(ptr(l), ptr(r), N, Hl, Wl, s, H, W, int(valid_hw[0]), int(valid_hw[1]), float(lr_max_diff),
                                ptr(out), ptr(mask), current_stream()), 'st_lr_check_pack')
     torch.cuda.synchronize()
@@ -102,8 +103,8 @@ def assert_pack_equals_restatement(dL, dR, s, valid_hw, lr_max_diff, cuda):
     assert same(got2, got)
     # a valid pixel keeps the bits st_disp_upsample_pack writes on the same input
     N, Hl, Wl = dL.shape
-    l = torch.from_numpy(np.array(dL, np.float32)).to(cuda)
-    up = torch.full((N, 3, Hl * s, Wl * s), float('nan'), device=cuda)
+    l = gm.device_input(np.array(dL, np.float32), cuda)
+    up = gm.device_output((N, 3, Hl * s, Wl * s), cuda, float('nan'))
     check(lib.st_disp_upsample_pack(ptr(l), N, Hl, Wl, s, Hl * s, Wl * s, int(valid_hw[0]), int(valid_hw[1]), ptr(up),
                                     current_stream()))
     torch.cuda.synchronize()
@@ -352,3 +353,16 @@ def test_lrcheck_config_through_the_shell_masks_the_per_box_depth(cuda):
     torch.cuda.synchronize()
     for n in range(2):
         assert torch.equal(outs[n].pred_det_instances.bboxes.cpu(), ref_boxes[n])
+
+
+# the entry points alone (st_softargmin_right, st_lr_check_pack, st_disp_upsample_pack) on their own case tables
+GUARDED = [test_softargmin_right_bit_equal_to_restatement, test_lr_check_pack_bit_equal_to_restatement,
+           test_lr_check_pack_odd_widths_and_non_finite_disparities, test_lr_check_pack_is_strict_at_equality]
+NAN_BY_CONTRACT = [test_lr_check_pack_odd_widths_and_non_finite_disparities]      # a valid pixel beside a NaN input is NaN
+
+
+# ---- the same entry points over hostile surroundings (tests/guard_memory.py) -------------------------------------------
+test_entry_points_are_blind_to_guard_bands = gm.guarded_test(GUARDED, NAN_BY_CONTRACT, doc="""Each test above twice (guard_memory.run_both): as it stands, and with the volume, both disparity maps and
+    every output buffer between guard bands of 0xFF bytes (the diagonal gather's x + d past the row, the bilinear
+    taps' y = -1 and x = -1 land in NaN).  The hostile run passes the test's own bit-exact bar against the restatement
+    and equals the friendly run bit for bit; bands and inputs are unchanged bytewise.""")

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import guard_memory as gm
 from oracle import resize as orz
 from stereotracking_amd import datasets as ds
 from stereotracking_amd._lib import check, load, ptr
@@ -21,22 +22,22 @@ def test_resize_planes_bit_exact_against_the_restatement(h, w, h2, w2, cuda):
     lib = load()
     rng = np.random.RandomState(h + w2)
     img = rng.randint(0, 256, (h, w, 3)).astype(np.uint8)
-    src = torch.from_numpy(img).to(cuda)
+    src = gm.device_input(img, cuda)
     # interleaved (h, w, 3), as the decoder yields frames
-    dst = torch.empty(h2, w2, 3, dtype=torch.uint8, device=cuda)
+    dst = gm.device_output((h2, w2, 3), cuda, 0, torch.uint8)
     check(lib.st_resize_planes(ptr(src), 3, h, w, 1, ptr(dst), h2, w2, 1, 1, None), 'st_resize_planes')
     want = orz.resize_bilinear_u8(img, h2, w2)
     assert np.array_equal(dst.cpu().numpy(), want)
     # planar (3, h, w), as the sequence drivers keep them: the same values plane by plane
-    srcp = src.permute(2, 0, 1).contiguous()
-    dstp = torch.empty(3, h2, w2, dtype=torch.uint8, device=cuda)
+    srcp = gm.device_input(img.transpose(2, 0, 1).copy(), cuda)
+    dstp = gm.device_output((3, h2, w2), cuda, 0, torch.uint8)
     check(lib.st_resize_planes(ptr(srcp), 3, h, w, 0, ptr(dstp), h2, w2, 1, 1, None), 'st_resize_planes')
     assert np.array_equal(dstp.cpu().numpy(), want.transpose(2, 0, 1))
     # nearest: uint16 codes (2 bytes), fp32 maps (4 bytes), uint8 masks (1 byte)
     codes = rng.randint(0, 65536, (h, w)).astype(np.uint16)
     for arr in (codes, (codes / 16.0).astype(np.float32), (codes < 60000).astype(np.uint8)):
-        t = torch.from_numpy(arr.view(np.int16) if arr.dtype == np.uint16 else arr).to(cuda)
-        o = torch.empty(h2, w2, dtype=t.dtype, device=cuda)
+        t = gm.device_input(arr.view(np.int16) if arr.dtype == np.uint16 else arr, cuda)
+        o = gm.device_output((h2, w2), cuda, 0, t.dtype)
         check(lib.st_resize_planes(ptr(t), 1, h, w, 0, ptr(o), h2, w2, t.element_size(), 0, None), 'st_resize_planes')
         got = o.cpu().numpy()
         assert np.array_equal(got.view(arr.dtype) if arr.dtype == np.uint16 else got, orz.resize_nearest(arr, h2, w2))
@@ -77,3 +78,13 @@ def test_resize_disparity_transform_non_identity_scale(cuda):
     # the identity scale touches nothing
     same = ds.Resize_Disparity(scale=(1280, 720))(dict(res))
     assert same['img'] is img and same['scale_factor'] == (1.0, 1.0)
+
+
+GUARDED = [test_resize_planes_bit_exact_against_the_restatement]      # st_resize_planes, every element size
+NAN_BY_CONTRACT = []
+
+
+# ---- the same entry points over hostile surroundings (tests/guard_memory.py) -------------------------------------------
+test_entry_points_are_blind_to_guard_bands = gm.guarded_test(GUARDED, NAN_BY_CONTRACT, doc="""st_resize_planes twice (guard_memory.run_both): as it stands, and with source and destination planes between
+    guard bands of 0xFF bytes (a replicated border that is read one pixel outside instead lands in 255 / NaN / -1).
+    The hostile run passes the bit-exact bar against the restatement and equals the friendly run byte for byte.""")

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import guard_memory as gm
 from oracle import c_oracle
 from oracle import depth as odepth
 from parity_utils import rel_err
@@ -24,9 +25,9 @@ pytestmark = pytest.mark.gpu
 def run_costvolume(fl, fr, Cc, D, T, cuda, want_cost=True):
     lib = _lib.load()
     N, Hf, Wf, ld = fl.shape
-    l, r = torch.from_numpy(fl).to(cuda), torch.from_numpy(fr).to(cuda)
-    cost = torch.full((N, Hf, Wf, D), float('nan'), device=cuda) if want_cost else None
-    disp = torch.full((N, Hf, Wf), float('nan'), device=cuda)
+    l, r = gm.device_input(fl, cuda, 0, Cc), gm.device_input(fr, cuda, 0, Cc)   # channels past Cc: slack
+    cost = gm.device_output((N, Hf, Wf, D), cuda, float('nan')) if want_cost else None
+    disp = gm.device_output((N, Hf, Wf), cuda, float('nan'))
     check(lib.st_costvolume_softargmin(ptr(l), ptr(r), N, Hf, Wf, Cc, ld, D, T, ptr(cost), ptr(disp),
                                        current_stream()))
     torch.cuda.synchronize()
@@ -50,8 +51,8 @@ def test_costvolume_bit_exact_and_softargmin(N, Hf, Wf, Cc, ld, D, cuda):
     assert np.array_equal(disp, disp2)
     # stand-alone soft-argmin on the materialised volume: sequential order => bit-exact
     lib = _lib.load()
-    c = torch.from_numpy(ref_cost).to(cuda)
-    o = torch.empty(N, Hf, Wf, device=cuda)
+    c = gm.device_input(ref_cost, cuda)
+    o = gm.device_output((N, Hf, Wf), cuda, float('nan'))
     check(lib.st_softargmin(ptr(c), N, Hf, Wf, D, T, ptr(o), current_stream()))
     torch.cuda.synchronize()
     assert np.array_equal(o.cpu().numpy().view(np.uint32), ref_disp.view(np.uint32))
@@ -133,8 +134,8 @@ def test_wide_volume_materialised_in_slabs_is_bit_exact(N, Hf, Wf, Cc, D, cuda):
     fr = rng.normal(0, 1, (N, Hf, Wf, Cc)).astype(np.float32)
     ref = c_oracle.costvolume(fl, fr, Cc, D)
     lib = _lib.load()
-    l, r = torch.from_numpy(fl).to(cuda), torch.from_numpy(fr).to(cuda)
-    cost = torch.full((N, Hf, Wf, D), float('nan'), device=cuda)
+    l, r = gm.device_input(fl, cuda), gm.device_input(fr, cuda)
+    cost = gm.device_output((N, Hf, Wf, D), cuda, float('nan'))
     check(lib.st_costvolume_softargmin(ptr(l), ptr(r), N, Hf, Wf, Cc, Cc, D, 1.0, ptr(cost), None, current_stream()))
     torch.cuda.synchronize()
     assert np.array_equal(cost.cpu().numpy().view(np.uint32), ref.view(np.uint32))
@@ -162,8 +163,8 @@ def test_upsample_pack_bit_exact_and_matches_torch(Hf, Wf, s, cut_h, cut_w, cuda
     H, W, vh, vw = Hf * s, Wf * s, Hf * s - cut_h, Wf * s - cut_w
     ref = c_oracle.disp_upsample(lr, s, vh, vw)
     lib = _lib.load()
-    out = torch.full((N, 3, H, W), float('nan'), device=cuda)
-    lr_dev = torch.from_numpy(lr).to(cuda)  # keep alive: ptr() does not hold a reference
+    out = gm.device_output((N, 3, H, W), cuda, float('nan'))
+    lr_dev = gm.device_input(lr, cuda)  # keep alive: ptr() does not hold a reference
     check(lib.st_disp_upsample_pack(ptr(lr_dev), N, Hf, Wf, s, H, W, vh, vw, ptr(out),
                                     current_stream()))
     torch.cuda.synchronize()
@@ -191,12 +192,12 @@ def run_box_depth(disp3, boxes, counts, cuda, baseline=0.25, focal=640.0):
     lib = _lib.load()
     N, _, H, W = disp3.shape
     M = boxes.shape[1]
-    d = torch.from_numpy(disp3).to(cuda)
-    b = torch.from_numpy(boxes).to(cuda)
-    c = torch.from_numpy(counts).to(cuda)
-    depth = torch.full((N, M), -7.0, device=cuda)
-    scale = torch.full((N, M), -7.0, device=cuda)
-    sb = torch.full((N, M, 4), -7.0, device=cuda)
+    d = gm.device_input(disp3, cuda)
+    b = gm.device_input(boxes, cuda)
+    c = gm.device_input(counts, cuda)
+    depth = gm.device_output((N, M), cuda, -7.0)
+    scale = gm.device_output((N, M), cuda, -7.0)
+    sb = gm.device_output((N, M, 4), cuda, -7.0)
     check(lib.st_box_depth(ptr(d), 3 * H * W, N, H, W, ptr(b), ptr(c), M, baseline, focal, None, 0, current_stream(),
                            ptr(depth), ptr(scale), ptr(sb)))
     torch.cuda.synchronize()
@@ -275,8 +276,10 @@ def test_pack_raw_inputs_matches_reference_pipeline(h, w, cuda):
     img = rng.randint(0, 256, (N, 3, h, w)).astype(np.uint8)
     code = rng.randint(0, 48 * 16, (N, h, w)).astype(np.uint16)
     code[rng.uniform(size=code.shape) < 0.1] = 65535
-    out = pack_raw_inputs(torch.from_numpy(img).to(cuda), torch.from_numpy(code.view(np.int16)).to(cuda))
+    out = pack_raw_inputs(gm.device_input(img, cuda), gm.device_input(code.view(np.int16), cuda))
     torch.cuda.synchronize()
+    for key in ('img', 'disp_postp', 'disp_mask'):
+        gm.current().track(out[key])
     H, W = 64, 96
     # numpy restatement of the reference transforms
     disp = code.astype(np.float32)
@@ -302,12 +305,12 @@ def test_raw_frames_chunk_pointer_table(h, w, B, n, cuda):
     the last frame repeated up to the batch size; a non-contiguous frame takes the torch.cat route, same values."""
     from stereotracking_amd.mot import RawFrames
     rng = np.random.RandomState(11)
-    frames = [torch.from_numpy(rng.randint(0, 256, (1, 3, h, w)).astype(np.uint8)).to(cuda) for _ in range(n)]
+    frames = [gm.device_input(rng.randint(0, 256, (1, 3, h, w)).astype(np.uint8), cuda) for _ in range(n)]
     H, W = (h + 31) // 32 * 32, (w + 31) // 32 * 32
     ref = torch.full((B, 3, H, W), 114.0, device=cuda)
     for i in range(B):
         ref[i, :, :h, :w] = frames[min(i, n - 1)][0].float()
-    out = RawFrames(frames, (H, W), 114.0).chunk(0, n, B)
+    out = gm.current().track(RawFrames(frames, (H, W), 114.0).chunk(0, n, B))
     assert torch.equal(out, ref)
     strided = list(frames)
     strided[1] = torch.stack([frames[1][0], frames[1][0]], 1)[:, 0][None]      # a non-contiguous view of frame 1
@@ -368,8 +371,8 @@ def test_agg3d_layer_bit_exact(N, Hf, Wf, D, act, cuda):
     w = rng.normal(0, 0.4, (3, 3, 3)).astype(np.float32)
     bias = 0.125
     ref = c_oracle.agg3d(vol, w, bias, act)
-    src = torch.from_numpy(vol).to(cuda)
-    dst = torch.full_like(src, float('nan'))
+    src = gm.device_input(vol, cuda)
+    dst = gm.device_output(vol.shape, cuda, float('nan'))
     w27 = (C.c_float * 27)(*w.reshape(-1).tolist())
     check(lib.st_volume_agg3d(ptr(src), ptr(dst), N, Hf, Wf, D, w27, bias, act, current_stream()), 'st_volume_agg3d')
     torch.cuda.synchronize()
@@ -399,8 +402,8 @@ def test_costvolume_agg3d_fused_bit_exact(N, H, W, Cc, ld, D, act, cuda):
     bias = -0.0625
     ref = c_oracle.agg3d(c_oracle.costvolume(fl, fr, Cc, D), w, bias, act)
     assert lib.st_costvolume_agg3d_supported(Cc, D) == 1
-    gl, gr = torch.from_numpy(fl).to(cuda), torch.from_numpy(fr).to(cuda)
-    out = torch.full((N, H, W, D), float('nan'), device=cuda)
+    gl, gr = gm.device_input(fl, cuda, 0, Cc), gm.device_input(fr, cuda, 0, Cc)
+    out = gm.device_output((N, H, W, D), cuda, float('nan'))
     w27 = (C.c_float * 27)(*w.reshape(-1).tolist())
     check(lib.st_costvolume_agg3d(ptr(gl), ptr(gr), N, H, W, Cc, ld, D, w27, bias, act, ptr(out), current_stream()),
           'st_costvolume_agg3d')
@@ -437,9 +440,9 @@ def test_costvolume_agg3d_softargmin_single_kernel_bit_exact(N, H, W, Cc, ld, D,
     w = rng.normal(0, 0.4, (3, 3, 3)).astype(np.float32)
     bias, T = 0.03125, 32.0
     ref = c_oracle.softargmin(c_oracle.agg3d(c_oracle.costvolume(fl, fr, Cc, D), w, bias, act), T)
-    gl, gr = torch.from_numpy(fl).to(cuda), torch.from_numpy(fr).to(cuda)
+    gl, gr = gm.device_input(fl, cuda, 0, Cc), gm.device_input(fr, cuda, 0, Cc)
     w27 = (C.c_float * 27)(*w.reshape(-1).tolist())
-    disp = torch.full((N, H, W), float('nan'), device=cuda)
+    disp = gm.device_output((N, H, W), cuda, float('nan'))
     check(lib.st_costvolume_agg3d_softargmin(ptr(gl), ptr(gr), N, H, W, Cc, ld, D, w27, bias, act, T, ptr(disp),
                                              current_stream()), 'st_costvolume_agg3d_softargmin')
     torch.cuda.synchronize()
@@ -517,8 +520,8 @@ def test_softargmin_wide_volumes_bit_exact(N, Hf, Wf, D, cuda):
     vol = rng.normal(0, 0.6, (N, Hf, Wf, D)).astype(np.float32)
     for T in (4.0, 32.0):
         ref = c_oracle.softargmin(vol, T)
-        c = torch.from_numpy(vol).to(cuda)
-        o = torch.full((N, Hf, Wf), float('nan'), device=cuda)
+        c = gm.device_input(vol, cuda)
+        o = gm.device_output((N, Hf, Wf), cuda, float('nan'))
         check(lib.st_softargmin(ptr(c), N, Hf, Wf, D, T, ptr(o), current_stream()))
         torch.cuda.synchronize()
         assert np.array_equal(o.cpu().numpy().view(np.uint32), ref.view(np.uint32)), (D, T)
@@ -622,8 +625,8 @@ def test_feat_upsample_bit_exact(N, Hf, Wf, C_, ld, scale, cuda):
     rng = np.random.RandomState(Hf * 10 + Wf)
     feat = rng.normal(0, 1, (N, Hf, Wf, ld)).astype(np.float32)
     ref = c_oracle.feat_upsample(feat, scale, C_)
-    src = torch.from_numpy(feat).to(cuda)
-    dst = torch.full((N, Hf * scale, Wf * scale, C_), float('nan'), device=cuda)
+    src = gm.device_input(feat, cuda, 0, C_)
+    dst = gm.device_output((N, Hf * scale, Wf * scale, C_), cuda, float('nan'))
     check(lib.st_feat_upsample(ptr(src), N, Hf, Wf, C_, ld, scale, ptr(dst), current_stream()), 'st_feat_upsample')
     torch.cuda.synchronize()
     got = dst.cpu().numpy()
@@ -713,3 +716,26 @@ def test_stereo_full_resolution_mode_matches_oracle(agg3d_layers, cuda):
     torch.cuda.synchronize()
     assert 'cost_volume' in sm.pop_full_res_times() and torch.equal(out3, out)
     sm.timing, sm.fuse_first_layer = False, True
+
+
+# ---- the same kernels over non-finite channel slack and inside guard bands (tests/guard_memory.py) --------------------
+GUARDED = [
+    test_costvolume_bit_exact_and_softargmin,                     # st_costvolume_softargmin (ld > Cc, both forms), st_softargmin
+    test_wide_volume_materialised_in_slabs_is_bit_exact,
+    test_upsample_pack_bit_exact_and_matches_torch,               # st_disp_upsample_pack
+    test_box_depth_matches_reference_semantics,                   # st_box_depth, the disparity map in an arena
+    test_pack_raw_inputs_matches_reference_pipeline,              # st_pack_raw_inputs
+    test_raw_frames_chunk_pointer_table,                          # st_pack_raw_frames
+    test_agg3d_layer_bit_exact,                                   # st_volume_agg3d
+    test_costvolume_agg3d_fused_bit_exact,                        # st_costvolume_agg3d (ld > Cc)
+    test_costvolume_agg3d_softargmin_single_kernel_bit_exact,     # st_costvolume_agg3d_softargmin
+    test_softargmin_wide_volumes_bit_exact,
+    test_feat_upsample_bit_exact,                                 # st_feat_upsample (ld > C)
+]
+
+
+test_stereo_kernels_are_blind_to_slack_and_guard_bands = gm.guarded_test(GUARDED, [test_box_depth_matches_reference_semantics], doc="""Each test above on its own case table, twice (guard_memory.run_both): as it stands, and with NaN / +Inf / -Inf in
+    the padding channels of the feature rows and every input and output buffer between guard bands of 0xFF bytes (a
+    y = -1 row, x - d < 0, the last pixel's K tail land in NaN).  The hostile run passes the test's own bar against the
+    C oracle and its output buffers equal the friendly run's bit for bit; bands and inputs are unchanged bytewise.
+    Box depth returns NaN by contract (an empty corner slice), so its outputs are compared as bits only.""")
