@@ -1218,6 +1218,69 @@ int st_batched_tracker_run(StBatchedTracker* t, const int32_t* frame_ids_dev, co
                            int32_t* out_counts_dev, int32_t* status_dev, st_stream_t stream);
 
 /* ----------------------------------------------------------------------
+ * 21. The MOTChallenge protocol of MOTDroneMetrics(protocol='trackeval') on the device, csrc/mot_eval.hip.  The rules
+ *     are the statements of stereotracking_amd/metrics.py motchallenge_file_rows and motchallenge_preprocess (DESIGN.md
+ *     section 21): the values a reader of the written text files gets, then TrackEval's MotChallenge2DBox preprocessing.
+ *     fp64 and integers throughout, no atomics on the outputs: two runs give the same bytes.
+ *
+ *  st_mot_file_round: elementwise over rows (num_rows, num_cols) fp64, out-of-place or in place (out_dev == rows_dev).
+ *    col_modes (num_cols <= ST_MOT_FILE_MAX_COLS ints, HOST memory): ST_MOT_FILE_COPY the value as it is;
+ *    ST_MOT_FILE_TRUNCATE int(v), toward zero (the '%d' columns); ST_MOT_FILE_ROUND3 float('%.3f' % v): the exact
+ *    binary value to 3 decimals, ties to even, then the nearest double to that decimal - from the exact residual of
+ *    v * 1000 (one fused multiply-add), never from rint(v * 1000) alone.
+ *    status: 8 ints on the device, zeroed by the call.  [0] bits: 1 a non-finite value in a TRUNCATE / ROUND3 column,
+ *    2 |v| >= 2^43 in a ROUND3 column (v * 1000 must stay below 2^53).  [1 + k] for bit 1 << k: num_rows - the row
+ *    index of the first offender.  An offending cell is copied unchanged.  Enqueued on `stream`, no host wait.
+ *
+ *  st_mot_challenge_preprocess: per frame with ground truth and predictions, one assignment on the IoU of the xywh
+ *    boxes with entries < 0.5 - eps zeroed; a prediction matched (weight > eps) to ground truth of a distractor class
+ *    is removed; ground truth is kept iff conf != 0 and class == 1.  do_preproc == 0 (MOT15): no matching, every
+ *    prediction kept, ground truth kept iff conf != 0.
+ *   rows     all sequences packed, sorted by sequence and frame.  gt_rows (num_gt, 8) fp64 = (frame, id, x, y, w, h,
+ *            conf, class); pred_rows (num_pred, 7) = (frame, id, x, y, w, h, score).  Only the boxes, conf and class are read.
+ *   tables   built by the host (stereotracking_amd/mot_eval.py) and TRUSTED: frame_gt_off / frame_pred_off
+ *            (num_frames + 1) first row of every frame; frame_ws_off (num_frames + 1, 64-bit) first cell of the frame's
+ *            slot in ws: a frame of more than 64 x 64 cells needs a slot of G x P cells, any other may have an empty
+ *            one (solved out of LDS); num_ws_cells = frame_ws_off[num_frames].  distractors: num_distractors <=
+ *            ST_MOT_CHALLENGE_MAX_DISTRACTORS class ids.
+ *   limits   at most ST_MOT_MAX_OBJECTS rows of either kind in one frame.
+ *   status   8 ints, 0 = fine, zeroed by the call, the bits of section 16: 1 non-finite box, 8 a frame above the limit,
+ *            32 a frame whose ws slot is too small.  [1 + k] for bit 1 << k: num_frames - the frame index of the first
+ *            offender.  The frames that set a bit write nothing.
+ *   outputs  gt_keep (num_gt) / pred_keep (num_pred) bytes, 1 = the row is scored.  Both are zeroed by the call.
+ *   One stage, enqueued on `stream`, one kernel launch (one wave per frame), no host wait.
+ *   ws: caller-owned, st_mot_challenge_workspace_bytes(args) (0: invalid sizes).
+ * ---------------------------------------------------------------------- */
+#define ST_MOT_FILE_COPY 0
+#define ST_MOT_FILE_TRUNCATE 1
+#define ST_MOT_FILE_ROUND3 2
+#define ST_MOT_FILE_MAX_COLS 16
+#define ST_MOT_CHALLENGE_MAX_DISTRACTORS 8
+typedef struct StMotChallengeArgs {
+  int struct_size;              /* sizeof(StMotChallengeArgs) */
+  int num_frames, num_gt, num_pred;
+  int max_frame_objects;        /* largest number of gt or prediction rows in one frame; 0: unknown */
+  int do_preproc;               /* 0: MOT15 */
+  int num_distractors;
+  int distractors[ST_MOT_CHALLENGE_MAX_DISTRACTORS];
+  long long num_ws_cells;       /* frame_ws_off[num_frames] */
+  const double* gt_rows;
+  const double* pred_rows;
+  const int* frame_gt_off;
+  const int* frame_pred_off;
+  const long long* frame_ws_off;
+  void* ws;
+  size_t ws_bytes;
+  unsigned char* gt_keep;
+  unsigned char* pred_keep;
+  int* status;
+} StMotChallengeArgs;
+int st_mot_file_round(const double* rows_dev, double* out_dev, long long num_rows, int num_cols, const int* col_modes,
+                      int* status_dev, st_stream_t stream);
+size_t st_mot_challenge_workspace_bytes(const StMotChallengeArgs* args);
+int st_mot_challenge_preprocess(const StMotChallengeArgs* args, st_stream_t stream);
+
+/* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call
  * (mmtrack/datasets/transforms/loading_disparity.py:74-75 uint16 disparity, :213-215 uint16 depth; mmcv's

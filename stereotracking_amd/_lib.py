@@ -151,6 +151,13 @@ class StMotKittiArgs(C.Structure):
         [(n, C.c_void_p) for n in ('gt_keep', 'pred_keep', 'status')]
 
 
+class StMotChallengeArgs(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('struct_size', 'num_frames', 'num_gt', 'num_pred', 'max_frame_objects', 'do_preproc',
+                                       'num_distractors')] + [('distractors', C.c_int * 8), ('num_ws_cells', C.c_longlong)] + \
+        [(n, C.c_void_p) for n in ('gt_rows', 'pred_rows', 'frame_gt_off', 'frame_pred_off', 'frame_ws_off', 'ws')] + \
+        [('ws_bytes', C.c_size_t)] + [(n, C.c_void_p) for n in ('gt_keep', 'pred_keep', 'status')]
+
+
 class StTrackletArgs(C.Structure):
     _fields_ = [(n, C.c_int) for n in ('struct_size', 'num_rows', 'num_out_rows', 'num_tracks', 'first', 'count',
                                        'num_groups', 'max_rows')] + \
@@ -324,6 +331,9 @@ _PROTOS = {
     'st_mot_hota_accumulate': (_i, [C.POINTER(StMotArgs), _vp]),
     'st_mot_kitti_workspace_bytes': (_sz, [C.POINTER(StMotKittiArgs)]),
     'st_mot_kitti_preprocess': (_i, [C.POINTER(StMotKittiArgs), _vp]),
+    'st_mot_file_round': (_i, [_vp, _vp, C.c_longlong, _i, C.POINTER(C.c_int), _vp, _vp]),
+    'st_mot_challenge_workspace_bytes': (_sz, [C.POINTER(StMotChallengeArgs)]),
+    'st_mot_challenge_preprocess': (_i, [C.POINTER(StMotChallengeArgs), _vp]),
     'st_tracklet_max_rows': (_i, []),
     'st_tracklet_gsi_workspace_bytes': (_sz, [C.POINTER(StTrackletArgs)]),
     'st_tracklet_interpolate': (_i, [C.POINTER(StTrackletArgs), _vp]),

@@ -17,7 +17,12 @@
 //   kitti_preprocess k_kitti        one wave per (frame, class): KITTI's 2-D box preprocessing behind st_mot_kitti_preprocess
 //                                   (section 16): class split by ballots, thresholded IoU, one assignment, the keep bytes
 //
-// One solver serves k_walk, k_hota_match and k_kitti: solve_assignment, the shortest-augmenting-path (Jonker-Volgenant /
+//   file_round       k_file_round   elementwise: what a reader of the MOTChallenge text files gets ('%d' / '%.3f' per column),
+//                                   behind st_mot_file_round (section 21)
+//   challenge_prep.  k_challenge    one wave per frame: TrackEval's MOTChallenge preprocessing behind
+//                                   st_mot_challenge_preprocess (section 21): IoU thresholded at 0.5, one assignment, keep bytes
+//
+// One solver serves k_walk, k_hota_match, k_kitti and k_challenge: solve_assignment, the shortest-augmenting-path (Jonker-Volgenant /
 // Hungarian) method for one wave, exact on a rectangular matrix of non-negative fp64 weights.
 #include <climits>
 #include <cmath>
@@ -681,6 +686,149 @@ __global__ __launch_bounds__(64) void k_kitti(StMotKittiArgs a, double* ws, int 
   }
 }
 
+// ---- MOTChallenge protocol (include/stereotrack.h section 21, metrics.py motchallenge_file_rows / _preprocess) ----------
+constexpr int kModeCopy = ST_MOT_FILE_COPY, kModeTrunc = ST_MOT_FILE_TRUNCATE, kModeRound3 = ST_MOT_FILE_ROUND3;
+constexpr int kFileCols = ST_MOT_FILE_MAX_COLS;
+constexpr int kTooLarge = 2;                                    // st_mot_file_round's status bit: |x| >= 2^43 in a round3 column
+constexpr double kRound3Limit = 8796093022208.0;                // 2^43: x * 1000 stays below 2^53
+constexpr int kChGtCols = 8, kChPredCols = 7;                   // (frame, id, x, y, w, h, conf, class) / (..., score)
+constexpr int kChMaxDistractors = ST_MOT_CHALLENGE_MAX_DISTRACTORS;
+
+struct FileModes { int m[kFileCols]; };
+
+// float('%.3f' % x): the EXACT value of x to 3 decimals, ties to even, then the nearest double to that decimal.
+// p = x * 1000 is rounded; e = the exact residual x * 1000 - p (one fused multiply-add); n = rint(p) is the candidate
+// and the exact distance of x * 1000 from n is d + e with d = p - n exact (|d| <= 0.5).  The candidate is off by one
+// where d + e lies beyond +-0.5, and on an exact tie the even neighbour is taken.
+__device__ inline double round3(double x) {
+  const double p = x * 1000.0;
+  const double e = __builtin_fma(x, 1000.0, -p);
+  double n = rint(p);
+  const double d = p - n;
+  const double hi = (d - 0.5) + e, lo = (d + 0.5) + e;
+  const bool odd = (((long long)n) & 1ll) != 0;
+  if (hi > 0.0 || (hi == 0.0 && odd)) n += 1.0;
+  else if (lo < 0.0 || (lo == 0.0 && odd)) n -= 1.0;
+  return n / 1000.0;
+}
+
+__global__ __launch_bounds__(256) void k_file_round(const double* __restrict__ rows, double* __restrict__ out, i64 num_rows,
+                                                    int cols, FileModes modes, int* status) {
+  const i64 total = num_rows * cols;
+  for (i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (i64)gridDim.x * blockDim.x) {
+    const i64 r = c / cols;
+    const int mode = modes.m[(int)(c - r * cols)];
+    const double x = rows[c];
+    const int rep = (int)(num_rows - r);
+    double y = x;
+    if (mode != kModeCopy) {
+      if (!isfinite(x)) {
+        report(status, kNonFinite, 0, rep);
+      } else if (mode == kModeTrunc) {
+        y = trunc(x) + 0.0;                                    // + 0.0: int(-0.5) is 0, not -0
+      } else if (fabs(x) >= kRound3Limit) {
+        report(status, kTooLarge, 1, rep);
+      } else {
+        y = round3(x);
+      }
+    }
+    out[c] = y;
+  }
+}
+
+// One wave per frame: TrackEval's MotChallenge2DBox preprocessing as metrics.motchallenge_preprocess states it.
+// S.used[j]: 1 = prediction j of the frame is matched to ground truth of a distractor class and removed.
+__global__ __launch_bounds__(64) void k_challenge(StMotChallengeArgs a, double* ws, int lds_cells) {
+  SolverLds& S = *reinterpret_cast<SolverLds*>(mot_smem);
+  double* Wl = reinterpret_cast<double*>(mot_smem + kSolverBytes);
+  const int f = blockIdx.x, lane = threadIdx.x;
+  const int rep = a.num_frames - f;
+  const int gs = a.frame_gt_off[f], ge = a.frame_gt_off[f + 1];
+  const int ps = a.frame_pred_off[f], pe = a.frame_pred_off[f + 1];
+  if (gs < 0 || ge < gs || ge > a.num_gt || ps < 0 || pe < ps || pe > a.num_pred) {
+    if (lane == 0) report(a.status, kFrameLimit, 3, rep);      // an offset table that does not fit the row arrays
+    return;
+  }
+  const int G = ge - gs, P = pe - ps;
+  if (G > kMaxObj || P > kMaxObj) {
+    if (lane == 0) report(a.status, kFrameLimit, 3, rep);
+    return;
+  }
+  bool bad = false;
+  for (int r = gs + lane; r < ge; r += 64) bad = bad || !finite_box(a.gt_rows + (size_t)kChGtCols * r + 2);
+  for (int r = ps + lane; r < pe; r += 64) bad = bad || !finite_box(a.pred_rows + (size_t)kChPredCols * r + 2);
+  if (bad) report(a.status, kNonFinite, 0, rep);
+  if (__any(bad)) return;
+
+  for (int i = lane; i < G; i += 64) {
+    const double* row = a.gt_rows + (size_t)kChGtCols * (gs + i);
+    if (row[6] != 0.0 && (!a.do_preproc || row[7] == 1.0)) a.gt_keep[gs + i] = 1;
+  }
+  const int cells = G * P;
+  const bool match = a.do_preproc && cells > 0;
+  if (match) {
+    double* W = Wl;
+    if (cells > lds_cells) {
+      const long long w0 = a.frame_ws_off[f], w1 = a.frame_ws_off[f + 1];
+      if (w0 < 0 || w1 > a.num_ws_cells || w1 - w0 < (long long)cells) {
+        if (lane == 0) report(a.status, kWsSlot, 5, rep);
+        return;
+      }
+      W = ws + (size_t)w0;
+    }
+    const double thr = 0.5 - kEps;                             // TrackEval's constant, not the scorers' iou_thr
+    for (int c = lane; c < cells; c += 64) {                   // box_iou_xywh, operation for operation
+      const int i = c / P, j = c - i * P;
+      const double* g = a.gt_rows + (size_t)kChGtCols * (gs + i) + 2;
+      const double* p = a.pred_rows + (size_t)kChPredCols * (ps + j) + 2;
+      const double ax2 = g[0] + g[2], ay2 = g[1] + g[3], bx2 = p[0] + p[2], by2 = p[1] + p[3];
+      double iw = fmin(ax2, bx2) - fmax(g[0], p[0]);
+      double ih = fmin(ay2, by2) - fmax(g[1], p[1]);
+      iw = iw < 0.0 ? 0.0 : iw;
+      ih = ih < 0.0 ? 0.0 : ih;
+      const double inter = iw * ih;
+      const double uni = (g[2] * g[3] + p[2] * p[3]) - inter;
+      const double sv = uni > 0.0 ? inter / fmax(uni, 1e-12) : 0.0;
+      W[c] = sv < thr ? 0.0 : sv;
+    }
+    __syncthreads();
+    solve_assignment(W, G, P, S, lane);
+    for (int j = lane; j < P; j += 64) S.used[j] = 0;
+    __syncthreads();
+    for (int i = lane; i < G; i += 64) {
+      const int j = S.mcol[i];
+      if (j < 0 || !(W[(size_t)i * P + j] > kEps)) continue;
+      const double cls = a.gt_rows[(size_t)kChGtCols * (gs + i) + 7];
+      bool distractor = false;
+      for (int k = 0; k < kChMaxDistractors; ++k) distractor = distractor || (k < a.num_distractors && cls == (double)a.distractors[k]);
+      if (distractor) S.used[j] = 1;                           // the columns of an assignment are distinct
+    }
+    __syncthreads();
+  }
+  for (int j = lane; j < P; j += 64)
+    if (!(match && S.used[j])) a.pred_keep[ps + j] = 1;
+}
+
+int validate_challenge(const StMotChallengeArgs* a) {
+  ST_REQUIRE(a != nullptr, "st_mot_challenge: args is NULL");
+  ST_REQUIRE(a->struct_size == (int)sizeof(StMotChallengeArgs), "st_mot_challenge: struct_size %d != %d", a->struct_size,
+             (int)sizeof(StMotChallengeArgs));
+  ST_REQUIRE(a->num_frames >= 0 && a->num_gt >= 0 && a->num_pred >= 0,
+             "st_mot_challenge: num_frames %d / num_gt %d / num_pred %d must be >= 0", a->num_frames, a->num_gt, a->num_pred);
+  ST_REQUIRE(a->num_distractors >= 0 && a->num_distractors <= kChMaxDistractors,
+             "st_mot_challenge: num_distractors %d outside 0..%d", a->num_distractors, kChMaxDistractors);
+  ST_REQUIRE(a->num_ws_cells >= 0, "st_mot_challenge: num_ws_cells must be >= 0");
+  ST_REQUIRE(a->ws != nullptr && a->ws_bytes >= st_mot_challenge_workspace_bytes(a),
+             "st_mot_challenge: workspace %zu < %zu bytes", a->ws_bytes, st_mot_challenge_workspace_bytes(a));
+  ST_REQUIRE(a->status != nullptr && (a->num_gt == 0 || a->gt_keep != nullptr) && (a->num_pred == 0 || a->pred_keep != nullptr),
+             "st_mot_challenge: status / gt_keep / pred_keep is NULL");
+  ST_REQUIRE((a->num_gt == 0 || a->gt_rows != nullptr) && (a->num_pred == 0 || a->pred_rows != nullptr),
+             "st_mot_challenge: gt_rows / pred_rows is NULL");
+  ST_REQUIRE(a->num_frames == 0 || (a->frame_gt_off && a->frame_pred_off && a->frame_ws_off),
+             "st_mot_challenge: an offset table is NULL");
+  return ST_OK;
+}
+
 int validate_kitti(const StMotKittiArgs* a) {
   ST_REQUIRE(a != nullptr, "st_mot_kitti: args is NULL");
   ST_REQUIRE(a->struct_size == (int)sizeof(StMotKittiArgs), "st_mot_kitti: struct_size %d != %d", a->struct_size,
@@ -828,6 +976,51 @@ int st_mot_kitti_preprocess(const StMotKittiArgs* a, st_stream_t stream_) {
   if (a->num_frames > 0)
     hipLaunchKernelGGL(k_kitti, dim3(a->num_frames * a->num_classes), dim3(64), kSolverBytes + lds_cells * sizeof(double),
                        stream, *a, (double*)a->ws, lds_cells);
+  ST_CHECK_HIP(hipGetLastError());
+  return ST_OK;
+}
+
+int st_mot_file_round(const double* rows_dev, double* out_dev, long long num_rows, int num_cols, const int* col_modes,
+                      int* status_dev, st_stream_t stream_) {
+  ST_REQUIRE(num_rows >= 0 && num_cols >= 1 && num_cols <= kFileCols, "st_mot_file_round: num_rows %lld must be >= 0, "
+             "num_cols %d in 1..%d", num_rows, num_cols, kFileCols);
+  ST_REQUIRE(num_rows < (1ll << 31) - 1, "st_mot_file_round: num_rows %lld: the status word holds 32-bit row numbers", num_rows);
+  ST_REQUIRE(col_modes != nullptr && status_dev != nullptr, "st_mot_file_round: col_modes / status is NULL");
+  ST_REQUIRE(num_rows == 0 || (rows_dev != nullptr && out_dev != nullptr), "st_mot_file_round: rows / out is NULL");
+  FileModes modes = {};
+  for (int c = 0; c < num_cols; ++c) {
+    ST_REQUIRE(col_modes[c] == kModeCopy || col_modes[c] == kModeTrunc || col_modes[c] == kModeRound3,
+               "st_mot_file_round: col_modes[%d] = %d is not a mode", c, col_modes[c]);
+    modes.m[c] = col_modes[c];
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  ST_CHECK(zero(status_dev, 0, 8 * sizeof(int), stream));
+  const long long total = num_rows * num_cols;
+  if (total > 0) {
+    const long long want = (total + 255) / 256;
+    hipLaunchKernelGGL(k_file_round, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, stream, rows_dev, out_dev,
+                       (i64)num_rows, num_cols, modes, status_dev);
+  }
+  ST_CHECK_HIP(hipGetLastError());
+  return ST_OK;
+}
+
+size_t st_mot_challenge_workspace_bytes(const StMotChallengeArgs* args) {
+  if (!args || args->struct_size != (int)sizeof(StMotChallengeArgs) || args->num_ws_cells < 0) return 0;
+  return align256(((size_t)args->num_ws_cells + 1) * sizeof(double));
+}
+
+int st_mot_challenge_preprocess(const StMotChallengeArgs* a, st_stream_t stream_) {
+  ST_CHECK(validate_challenge(a));
+  hipStream_t stream = (hipStream_t)stream_;
+  ST_CHECK(zero(a->status, 0, 8 * sizeof(int), stream));
+  ST_CHECK(zero(a->gt_keep, 0, (size_t)a->num_gt, stream));
+  ST_CHECK(zero(a->pred_keep, 0, (size_t)a->num_pred, stream));
+  const long long m = a->max_frame_objects;
+  const int lds_cells = m <= 0 ? 0 : (int)(m * m < kLdsCells ? m * m : kLdsCells);
+  if (a->num_frames > 0)
+    hipLaunchKernelGGL(k_challenge, dim3(a->num_frames), dim3(64), kSolverBytes + lds_cells * sizeof(double), stream, *a,
+                       (double*)a->ws, lds_cells);
   ST_CHECK_HIP(hipGetLastError());
   return ST_OK;
 }

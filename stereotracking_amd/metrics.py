@@ -14,6 +14,12 @@ previous frame's match; Identity - one global bipartite matching; HOTA - per-fra
 (global alignment score x IoU), thresholded per alpha, association accuracy per matched pair from the id-pair counts.
 Parity is UNPINNED against TrackEval itself (absent); the known-answer tests are hand-derived from the definitions.
 
+What is scored, MOTDroneMetrics(protocol=...): 'rows' (the default) scores the in-memory float rows as they were
+collected; 'trackeval' scores what the reference scores - the values a reader of the written MOTChallenge files gets
+(motchallenge_file_rows: ground truth '%d', predictions '%.3f', :223-253) after the preprocessing TrackEval's
+MotChallenge2DBox applies with CLASSES_TO_EVAL=['pedestrian'] and DO_PREPROC=True except for MOT15 (:273-289, :364-417;
+motchallenge_preprocess, restated [upstream-memory], parity UNPINNED).
+
 KITTI Tracking (stereotracking_amd/kitti_metrics.py, MOTKittiMetrics): kitti_box_ious and kitti_preprocess restate the
 preprocessing TrackEval applies to KITTI's 2-D boxes before these scorers see a sequence [upstream-memory].
 """
@@ -314,6 +320,119 @@ def kitti_preprocess(gt_rows, pred_rows, ignore_boxes, cls_id, distractor_ids, m
     return gt_keep, pred_keep
 
 
+PROTOCOLS = ('rows', 'trackeval')
+MOTCHALLENGE_BENCHMARKS = ('MOT15', 'MOT16', 'MOT17', 'MOT20', 'DanceTrack')      # mot_drone_metrics.py:84
+MOTCHALLENGE_NUM_CLASSES = 13         # MOTChallenge's class ids 1 .. 13; 1 = pedestrian, the one class evaluated
+_MOTCHALLENGE_DISTRACTORS = (2, 7, 8, 12)     # person_on_vehicle, static_person, distractor, reflection
+
+
+def motchallenge_distractors(benchmark):
+    """The distractor class ids of a benchmark; () where TrackEval does not preprocess (MOT15).  MOT20 adds 6
+    (non_mot_vehicle) [upstream-memory]."""
+    if benchmark not in MOTCHALLENGE_BENCHMARKS:
+        raise ValueError(f'benchmark must be one of {MOTCHALLENGE_BENCHMARKS}, got {benchmark!r}')
+    if benchmark == 'MOT15':
+        return ()
+    return _MOTCHALLENGE_DISTRACTORS + ((6,) if benchmark == 'MOT20' else ())
+
+
+def motchallenge_gt8(gt_rows):
+    """Ground-truth rows as (n, 8) fp64 (frame, id, x, y, w, h, conf, class): rows without the conf / class columns
+    (a sweep's 6-column ground truth) get conf 1, class 1; visibility is not scored and is dropped."""
+    rows = np.asarray(gt_rows, dtype=np.float64)
+    rows = rows.reshape(-1, rows.shape[-1]) if rows.size else np.zeros((0, 8))
+    if rows.shape[1] < 6:
+        raise ValueError(f'ground-truth rows need at least 6 columns, got {rows.shape[1]}')
+    if rows.shape[1] < 8:
+        rows = np.column_stack([rows, np.ones((len(rows), 8 - rows.shape[1]))])
+    return np.ascontiguousarray(rows[:, :8])
+
+
+def motchallenge_pred7(pred_rows):
+    """Prediction rows as (m, 7) fp64 (frame, id, x, y, w, h, score): 6-column rows get the score 1."""
+    rows = np.asarray(pred_rows, dtype=np.float64)
+    rows = rows.reshape(-1, rows.shape[-1]) if rows.size else np.zeros((0, 7))
+    if rows.shape[1] < 6:
+        raise ValueError(f'prediction rows need at least 6 columns, got {rows.shape[1]}')
+    if rows.shape[1] < 7:
+        rows = np.column_stack([rows, np.ones(len(rows))])
+    return np.ascontiguousarray(rows[:, :7])
+
+
+def _require_finite(rows, kind, video):
+    bad = np.nonzero(~np.isfinite(rows).all(axis=1))[0]
+    if len(bad):
+        where = '' if video is None else f'video {video!r}, '
+        raise ValueError(f'MOTChallenge files: a non-finite value: {where}{kind} row {int(bad[0])}')
+
+
+def motchallenge_file_rows(gt_rows, pred_rows, video=None):
+    """The values a reader of the files of write_motchallenge gets back (reference :223-253), without writing them.
+    Ground truth (frame, id, x, y, w, h, conf, class) is written with '%d': int(v), which truncates toward zero.
+    Predictions: frame and id with '%d', x, y, w, h and the score with '%.3f': float('%.3f' % v) - the EXACT binary
+    value to 3 decimals, ties to even, then the nearest double to that decimal.  np.rint(v * 1000) / 1000 is not that
+    (v * 1000 is rounded before rint sees it), so the predictions go through Python's own formatting, value by value:
+    the executable specification of st_mot_file_round.
+    A non-finite value raises ValueError naming `video` and the row ('%d' % nan raises in the reference).
+    Returns (gt (n, 8), pred (m, 7)) fp64 in the row order given (motchallenge_gt8 / motchallenge_pred7 widths)."""
+    gt, pred = motchallenge_gt8(gt_rows), motchallenge_pred7(pred_rows)
+    _require_finite(gt, 'ground-truth', video)
+    _require_finite(pred, 'prediction', video)
+    gt = np.trunc(gt) + 0.0                      # + 0.0: int(-0.5) is 0, not -0
+    out = np.empty_like(pred)
+    out[:, :2] = np.trunc(pred[:, :2]) + 0.0
+    out[:, 2:] = np.array([float('%.3f' % v) for v in pred[:, 2:].ravel().tolist()], dtype=np.float64).reshape(-1, 5)
+    return gt, out
+
+
+def motchallenge_preprocess(gt_rows, pred_rows, benchmark='MOT17'):
+    """The preprocessing of ONE sequence that TrackEval's MotChallenge2DBox.get_preprocessed_seq_data applies for the
+    class 'pedestrian' before a sequence is scored, restated from memory of that package [upstream-memory]; parity with
+    TrackEval itself (absent here) is UNPINNED.  The executable specification of st_mot_challenge_preprocess
+    (DESIGN.md section 21).
+
+    gt_rows (frame, id, x, y, w, h, conf, class, ...), pred_rows (frame, id, x, y, w, h, ...): what the files hold
+    (motchallenge_file_rows).  A ground-truth class outside 1 .. 13 raises ValueError.  Every benchmark but MOT15: per
+    frame with ground truth (of any class) and predictions, one assignment that maximises the sum of the IoU with
+    entries < 0.5 - eps zeroed (TrackEval's constant, not the scorers' iou_thr); a prediction matched (weight > eps) to
+    ground truth of a distractor class (motchallenge_distractors) is removed; ground truth is kept iff conf != 0 and
+    class == 1.  MOT15: no prediction is removed, ground truth is kept iff conf != 0.
+    Returns (gt_keep, pred_keep), boolean masks over the input rows.  The removed set is defined up to ties among the
+    optimal assignments that carry positive weight ("Ties")."""
+    eps = np.finfo(float).eps
+    distractors = list(motchallenge_distractors(benchmark))
+    gt, pred = motchallenge_gt8(gt_rows), motchallenge_pred7(pred_rows)
+    cls = gt[:, 7]
+    bad = np.nonzero(~((cls >= 1) & (cls <= MOTCHALLENGE_NUM_CLASSES) & (cls == np.floor(cls))))[0]
+    if len(bad):
+        raise ValueError(f'MOTChallenge preprocessing: ground-truth row {int(bad[0])} has class {cls[bad[0]]:g}, outside '
+                         f'1..{MOTCHALLENGE_NUM_CLASSES}')
+    pred_keep = np.ones(len(pred), dtype=bool)
+    if benchmark == 'MOT15':
+        return gt[:, 6] != 0, pred_keep
+    gf, pf = gt[:, 0].astype(np.int64), pred[:, 0].astype(np.int64)
+    for f in np.intersect1d(gf, pf):
+        gi, pi = np.nonzero(gf == f)[0], np.nonzero(pf == f)[0]
+        score = box_iou_xywh(gt[gi, 2:6], pred[pi, 2:6])
+        score[score < 0.5 - eps] = 0
+        rows, cols = linear_sum_assignment(-score)
+        ok = score[rows, cols] > 0 + eps
+        rows, cols = rows[ok], cols[ok]
+        pred_keep[pi[cols[np.isin(cls[gi[rows]], distractors)]]] = False
+    return (gt[:, 6] != 0) & (cls == 1), pred_keep
+
+
+def motchallenge_scored_rows(gt_by_video, pred_by_video, videos, benchmark='MOT17'):
+    """protocol='trackeval' on the host: video -> the file rows (motchallenge_file_rows) that motchallenge_preprocess
+    keeps, for both sides; what clear_identity / hota then score."""
+    gt, pred = {}, {}
+    for v in videos:
+        g, p = motchallenge_file_rows(gt_by_video.get(v, ()), pred_by_video.get(v, ()), video=v)
+        gk, pk = motchallenge_preprocess(g, p, benchmark)
+        gt[v], pred[v] = g[gk], p[pk]
+    return gt, pred
+
+
 def combine_videos(per_video, hota_by_video=None):
     """The combined result over videos (count-summed, like TrackEval's COMBINED_SEQ) of per-video clear_identity
     dicts.  hota_by_video: the videos' hota() dicts when HOTA is asked for (None: not asked); every video's dict then
@@ -387,9 +506,15 @@ class MOTDroneMetrics(GatheredVideoMetric):
     allowed_metrics = ('HOTA', 'CLEAR', 'Identity')
 
     def __init__(self, depth_thr=80, ignore_depth=False, iou_thr=0.5, metric=('HOTA', 'CLEAR', 'Identity'),
-                 backend='host', postprocess_tracklet_cfg=()):
+                 backend='host', postprocess_tracklet_cfg=(), protocol='rows', benchmark='MOT17'):
         _check_backend(backend)       # 'device': all videos in one mot_eval.evaluate_packed call, at evaluate()
         self.backend = backend
+        # 'rows': the collected float rows are scored; 'trackeval': what the reference's TrackEval run scores - the
+        # written files' values (motchallenge_file_rows) after motchallenge_preprocess for `benchmark` (:84, :273-289)
+        if protocol not in PROTOCOLS:
+            raise ValueError(f'protocol must be one of {PROTOCOLS}, got {protocol!r}')
+        motchallenge_distractors(benchmark)               # refuses a benchmark outside the reference's list
+        self.protocol, self.benchmark = protocol, benchmark
         # mot_drone_metrics.py:95, 110-113: TASK_UTILS entries applied to every video's prediction rows.  The reference
         # applies them in process() when a video's last frame arrives (:210-219); process() here has no video length,
         # so they run once per video at evaluation time (postprocessed_pred), after gather(), on the evaluating rank.
@@ -464,21 +589,45 @@ class MOTDroneMetrics(GatheredVideoMetric):
                 for t in rows:
                     f.write('%d,%d,%d,%d,%d,%d,%d,%d,%.5f\n' % tuple(t[:9]))
 
+    @classmethod
+    def read_motchallenge(cls, out_dir, **kwargs):
+        """A metric (built with `kwargs`) whose gt / pred hold what out_dir/gt/*.txt and out_dir/pred/*.txt, as
+        write_motchallenge wrote them, read back: every field through float(); the predictions' three trailing -1
+        fields are dropped.  The rows are final (tracklet post-processing ran before they were written)."""
+        m = cls(**kwargs)
+        for kind, store, width in (('gt', m.gt, 9), ('pred', m.pred, 7)):
+            folder = os.path.join(out_dir, kind)
+            for name in sorted(os.listdir(folder)) if os.path.isdir(folder) else ():
+                if not name.endswith('.txt'):
+                    continue
+                with open(os.path.join(folder, name), 'rt') as f:
+                    store[name[:-4]] = [[float(v) for v in line.split(',')[:width]] for line in f if line.strip()]
+        return m
+
     def _evaluate_local(self):
         videos = sorted(set(self.gt) | set(self.pred))
         pred = self.postprocessed_pred()
-        if self.backend == 'device':
+        gt = self.gt
+        wanted = ['CLEAR', 'Identity'] + (['HOTA'] if 'HOTA' in self.metrics else [])
+        if self.protocol == 'trackeval' and self.backend == 'device':
             from . import mot_eval
-            packed = mot_eval.pack_sequences({v: self.gt.get(v, []) for v in videos}, {v: pred.get(v, []) for v in videos})
-            wanted = ['CLEAR', 'Identity'] + (['HOTA'] if 'HOTA' in self.metrics else [])
+            scored = dict(zip(videos, mot_eval.evaluate_motchallenge(
+                [gt.get(v, []) for v in videos], [pred.get(v, []) for v in videos], self.benchmark, self.iou_thr, wanted,
+                videos=videos)))
+            per_video = {v: scored[v]['clear_identity'] for v in videos}
+        elif self.backend == 'device':
+            from . import mot_eval
+            packed = mot_eval.pack_sequences({v: gt.get(v, []) for v in videos}, {v: pred.get(v, []) for v in videos})
             scored = dict(zip(packed['videos'], mot_eval.evaluate_packed(packed, self.iou_thr, wanted)))
             per_video = {v: scored[v]['clear_identity'] for v in videos}
         else:
-            per_video = {v: clear_identity(self.gt.get(v, []), pred.get(v, []), self.iou_thr) for v in videos}
+            if self.protocol == 'trackeval':
+                gt, pred = motchallenge_scored_rows(gt, pred, videos, self.benchmark)
+            per_video = {v: clear_identity(gt.get(v, []), pred.get(v, []), self.iou_thr) for v in videos}
         hs = None
         if 'HOTA' in self.metrics:
             hs = {v: scored[v]['hota'] for v in per_video} if self.backend == 'device' else \
-                {v: hota(self.gt.get(v, []), pred.get(v, [])) for v in per_video}
+                {v: hota(gt.get(v, []), pred.get(v, [])) for v in per_video}
         return dict(per_video=per_video, combined=combine_videos(per_video, hs))
 
 

@@ -15,6 +15,12 @@ section 16) runs ahead of them for MOTKittiMetrics(backend
 
     masks = kitti_keep_masks(sequences, classes)               # one upload, one launch, one wait and copy back
 
+The MOTChallenge protocol of MOTDroneMetrics(protocol='trackeval') (metrics.motchallenge_file_rows / motchallenge_preprocess,
+the specification; st_mot_file_round / st_mot_challenge_preprocess, include/stereotrack.h section 21):
+
+    masks = motchallenge_keep_masks(gts, preds, 'MOT17')       # one upload, two roundings, one launch, one copy back
+    results = evaluate_motchallenge(gts, preds, 'MOT17')       # the same, then the kept rows through evaluate_packed
+
 Both backends are defined up to ties of the assignment optimum ("Ties").
 """
 import collections
@@ -136,6 +142,13 @@ class _Layout:
         return buf[off:off + n * dtype.itemsize].view(dtype).reshape(shape)
 
 
+def _device_view(layout, buf, name):
+    """_Layout.view for the device copy of the buffer (a uint8 tensor)."""
+    off, shape, dtype = layout.items[name]
+    n = int(np.prod(shape, dtype=np.int64))
+    return buf[off:off + n * dtype.itemsize].view(getattr(torch, dtype.name)).view(shape)
+
+
 def _where(packed, status, kind):
     f = int(packed['frame_no'].shape[0]) - int(status[1 + kind])
     return packed['videos'][int(packed['frame_seq'][f])], int(packed['frame_no'][f])
@@ -154,7 +167,7 @@ def _raise_status(packed, status):
 
 
 def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None, alphas=None, timing=False,
-                    return_arrays=False):
+                    return_arrays=False, device_boxes=None):
     """Scores every sequence of `packed` (pack_sequences) on the device.  Returns one dict per sequence, in the order of
     packed['videos']: 'clear_identity' = what metrics.clear_identity returns ('CLEAR' or 'Identity' in `metrics`, else
     None), 'hota' = what metrics.hota returns, per-alpha arrays included ('HOTA' in `metrics`, else None: the HOTA
@@ -162,7 +175,9 @@ def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), 
     `timing`: returns (results, timing dict) - HIP events around every stage and the host clock of the parts of the
     call.  `return_arrays`: every dict also carries 'arrays' with the
     device's intermediates of that sequence (sim: the IoU matrix of every frame, hota_potential, id_potential,
-    gt_count, tr_count) - one extra copy of the workspace, for tests."""
+    gt_count, tr_count) - one extra copy of the workspace, for tests.
+    `device_boxes`: (gt (num_gt, 4), pred (num_pred, 4)) fp64 tensors on the device that replace the x, y, w, h columns
+    of the packed rows after the upload (evaluate_motchallenge: boxes that never left the device)."""
     from . import metrics as M
     t_start = time.perf_counter()
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
@@ -194,6 +209,13 @@ def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), 
         lin.view(hbuf, k)[...] = v
     t_prep = time.perf_counter()
     dbuf = torch.from_numpy(hbuf).to(dev)
+    if device_boxes is not None:
+        for name, boxes in zip(('gt_rows', 'pred_rows'), device_boxes):
+            off, (n, _), _ = lin.items[name]
+            if tuple(boxes.shape) != (n, 4) or boxes.dtype != torch.float64 or boxes.device != dev:
+                raise ValueError(f'evaluate_packed: device_boxes for {name} must be ({n}, 4) float64 on {dev}')
+            if n:
+                dbuf[off:off + n * 48].view(torch.float64).view(n, 6)[:, 2:6] = boxes
 
     lout = _Layout()
     for name, shape, dt in (('status', (8,), np.int32), ('gt_count', (ids_g,), np.int32), ('tr_count', (ids_t,), np.int32),
@@ -435,6 +457,224 @@ def kitti_keep_masks(sequences, classes, max_occlusion=2, max_truncation=0, min_
     return out
 
 
+CHALLENGE_STATUS_KINDS = ((1, 0, 'a non-finite box'), (8, 3, 'more rows in one frame than a launch holds'),
+                          (32, 5, 'a workspace slot that is too small'))
+FILE_COPY, FILE_TRUNCATE, FILE_ROUND3 = 0, 1, 2          # ST_MOT_FILE_* of include/stereotrack.h section 21
+_FILE_MODES = dict(gt=(FILE_TRUNCATE,) * 8, pred=(FILE_TRUNCATE,) * 2 + (FILE_ROUND3,) * 5)
+_FILE_STATUS_KINDS = ((1, 0, 'a non-finite value'), (2, 1, 'a value of 2^43 or more in a column written with %.3f'))
+
+
+def file_round(rows_dev, modes, out_dev, status_dev):
+    """Enqueues st_mot_file_round on the current stream: rows_dev (n, len(modes)) fp64 on the device -> out_dev (the
+    same shape; may be rows_dev), status_dev = 8 int32 on the device.  No wait: the caller reads the status."""
+    n, cols = rows_dev.shape
+    if len(modes) != cols or rows_dev.dtype != torch.float64 or not rows_dev.is_contiguous() or not out_dev.is_contiguous():
+        raise ValueError(f'file_round: {tuple(rows_dev.shape)} {rows_dev.dtype} rows for {len(modes)} column modes')
+    LAUNCHES['st_mot_file_round'] += 1
+    check(_lib.load().st_mot_file_round(C.c_void_p(rows_dev.data_ptr()), C.c_void_p(out_dev.data_ptr()), n, cols,
+                                        (C.c_int * cols)(*modes), C.c_void_p(status_dev.data_ptr()), current_stream()),
+          'st_mot_file_round')
+
+
+def _challenge_device(gts, preds, benchmark, device, videos, timing):
+    """The device flow shared by motchallenge_keep_masks and evaluate_motchallenge: one upload, the two roundings, the
+    preprocessing, one wait and one copy back of the status words and the keep bytes."""
+    from . import metrics as M
+    t_start = time.perf_counter()
+    distractors = M.motchallenge_distractors(benchmark)
+    if not torch.cuda.is_available():
+        raise RuntimeError('the device backend of the MOTChallenge protocol runs on the HIP path only (csrc/mot_eval.hip) '
+                           'and no CUDA (ROCm) device is available; use backend=\'host\'')
+    lib = _lib.load()
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise RuntimeError(f'the device backend of the MOTChallenge protocol needs a CUDA (ROCm) device, got {dev}')
+    gts, preds = list(gts), list(preds)
+    if len(gts) != len(preds):
+        raise ValueError(f'MOTChallenge protocol: {len(gts)} ground-truth sets against {len(preds)} prediction sets')
+    videos = list(range(len(gts))) if videos is None else list(videos)
+
+    # ---- host tables, from the truncated frame column only; the class check needs the class column's integer part
+    parts, orders, frames_of, frame_no, frame_seq = ([], []), [], [], [], []
+    offs, totals = ([0], [0]), [0, 0]
+    for s, (g, p) in enumerate(zip(gts, preds)):
+        g, p = M.motchallenge_gt8(g), M.motchallenge_pred7(p)
+        M._require_finite(g, 'ground-truth', videos[s])
+        M._require_finite(p, 'prediction', videos[s])
+        cls = np.trunc(g[:, 7])
+        bad = np.nonzero((cls < 1) | (cls > M.MOTCHALLENGE_NUM_CLASSES))[0]
+        if len(bad):
+            raise ValueError(f'MOTChallenge preprocessing: video {videos[s]!r}: ground-truth row {int(bad[0])} has class '
+                             f'{cls[bad[0]]:g}, outside 1..{M.MOTCHALLENGE_NUM_CLASSES}')
+        srt = []
+        for rows in (g, p):
+            fr = np.trunc(rows[:, 0]).astype(np.int64)
+            order = np.argsort(fr, kind='stable')
+            srt.append((rows[order], fr[order], order))
+        frames = np.union1d(srt[0][1], srt[1][1])
+        for k, (rows, fr, _) in enumerate(srt):
+            parts[k].append(rows)
+            offs[k].append(totals[k] + np.searchsorted(fr, frames, 'right'))
+            totals[k] += len(rows)
+        orders.append((srt[0][2], srt[1][2]))
+        frames_of.append((srt[0][1], srt[1][1]))
+        frame_no.append(frames)
+        frame_seq.append(np.full(len(frames), s, np.int32))
+    frame_no = np.concatenate(frame_no + [np.zeros(0, np.int64)])
+    frame_seq = np.concatenate(frame_seq + [np.zeros(0, np.int32)])
+    F, (NG, NP_) = len(frame_no), totals
+    if max(NG, NP_, F) >= 2 ** 31 - 1:
+        raise ValueError(f'MOTChallenge protocol: {NG} ground-truth rows, {NP_} prediction rows, {F} frames: the offset tables '
+                         f'are 32-bit')
+    host_in = dict(gt_rows=np.concatenate(parts[0] + [np.zeros((0, 8))]), pred_rows=np.concatenate(parts[1] + [np.zeros((0, 7))]))
+    for k, name in enumerate(('frame_gt_off', 'frame_pred_off')):
+        host_in[name] = np.concatenate([np.atleast_1d(a) for a in offs[k]]).astype(np.int32)
+    G, P = np.diff(host_in['frame_gt_off']).astype(np.int64), np.diff(host_in['frame_pred_off']).astype(np.int64)
+    host_in['frame_ws_off'] = np.concatenate([[0], np.cumsum(np.where(G * P > _KITTI_LDS_CELLS, G * P, 0))]).astype(np.int64)
+
+    # ---- one upload
+    lin = _Layout()
+    for k, v in host_in.items():
+        lin.add(k, v.shape, v.dtype)
+    hbuf = np.zeros(lin.size, np.uint8)
+    for k, v in host_in.items():
+        lin.view(hbuf, k)[...] = v
+    t_prep = time.perf_counter()
+    dbuf = torch.from_numpy(hbuf).to(dev)
+    lout = _Layout()
+    for name, shape, dt in (('status_gt', (8,), np.int32), ('status_pred', (8,), np.int32), ('status', (8,), np.int32),
+                            ('gt_keep', (NG,), np.uint8), ('pred_keep', (NP_,), np.uint8)):
+        lout.add(name, shape, dt)
+    obuf = torch.empty(lout.size, dtype=torch.uint8, device=dev)       # the stages zero what they do not write
+    dview = lambda name: _device_view(lin, dbuf, name)
+    oview = lambda name: _device_view(lout, obuf, name)
+    gt_file = torch.empty((NG, 8), dtype=torch.float64, device=dev)    # the rows a reader of the files gets
+    pred_file = torch.empty((NP_, 7), dtype=torch.float64, device=dev)
+
+    args = _lib.StMotChallengeArgs()
+    args.struct_size = C.sizeof(_lib.StMotChallengeArgs)
+    args.num_frames, args.num_gt, args.num_pred = F, NG, NP_
+    args.max_frame_objects = int(max(G.max(initial=0), P.max(initial=0)))
+    args.do_preproc = int(benchmark != 'MOT15')
+    args.num_distractors = len(distractors)
+    for k, d in enumerate(distractors):
+        args.distractors[k] = int(d)
+    args.num_ws_cells = int(host_in['frame_ws_off'][-1])
+    args.gt_rows, args.pred_rows = C.c_void_p(gt_file.data_ptr()), C.c_void_p(pred_file.data_ptr())
+    for k in ('frame_gt_off', 'frame_pred_off', 'frame_ws_off'):
+        setattr(args, k, C.c_void_p(dbuf.data_ptr() + lin.items[k][0]))
+    for k in ('gt_keep', 'pred_keep', 'status'):
+        setattr(args, k, C.c_void_p(obuf.data_ptr() + lout.items[k][0]))
+    nbytes = int(lib.st_mot_challenge_workspace_bytes(C.byref(args)))
+    if nbytes == 0:
+        raise _lib.StError('st_mot_challenge_workspace_bytes: invalid sizes')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    args.ws, args.ws_bytes = C.c_void_p(ws.data_ptr()), nbytes
+    with torch.cuda.device(dev):
+        events = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing else None
+        if timing:
+            events[0].record()
+        file_round(dview('gt_rows'), _FILE_MODES['gt'], gt_file, oview('status_gt'))
+        file_round(dview('pred_rows'), _FILE_MODES['pred'], pred_file, oview('status_pred'))
+        if timing:
+            events[1].record()
+        LAUNCHES['st_mot_challenge_preprocess'] += 1
+        check(lib.st_mot_challenge_preprocess(C.byref(args), current_stream()), 'st_mot_challenge_preprocess')
+        if timing:
+            events[2].record()
+    host = obuf.cpu().numpy()          # the one wait and the one copy back
+    t_back = time.perf_counter()
+
+    def row_of(kind, packed_row):      # (video, index among the rows as they were passed) of a packed row
+        bounds = np.cumsum([0] + [len(o[kind]) for o in orders])
+        s = int(np.searchsorted(bounds, packed_row, 'right')) - 1
+        return videos[s], int(orders[s][kind][packed_row - bounds[s]])
+    for kind, (name, total) in enumerate((('status_gt', NG), ('status_pred', NP_))):
+        st = lout.view(host, name)
+        for bit, k, what in _FILE_STATUS_KINDS:
+            if int(st[0]) & bit:
+                video, row = row_of(kind, total - int(st[1 + k]))
+                raise ValueError(f'MOTChallenge files: {what}: video {video!r}, {("ground-truth", "prediction")[kind]} row {row}')
+        if st[0]:
+            raise _lib.StError(f'st_mot_file_round failed on the device: status {int(st[0])}')
+    status = lout.view(host, 'status')
+    if status[0]:
+        for bit, kind, what in CHALLENGE_STATUS_KINDS:
+            if int(status[0]) & bit:
+                f = F - int(status[1 + kind])
+                msg = f'MOTChallenge preprocessing: {what}: video {videos[int(frame_seq[f])]!r}, frame {int(frame_no[f])}'
+                if bit == 8:
+                    msg += f' (at most {max_frame_objects()} ground-truth and {max_frame_objects()} prediction rows per frame)'
+                raise ValueError(msg) if bit in (1, 8) else _lib.StError(msg)
+        raise _lib.StError(f'MOTChallenge preprocessing failed on the device: status {int(status[0])}')
+    out = dict(gt_file=gt_file, pred_file=pred_file, gt_keep=lout.view(host, 'gt_keep'), pred_keep=lout.view(host, 'pred_keep'),
+               orders=orders, frames_of=frames_of, sorted_rows=parts, videos=videos, device=dev)
+    if timing:
+        out['timing'] = dict(events=events, host_prepare_s=t_prep - t_start, device_and_copies_s=t_back - t_prep, t_back=t_back)
+    return out
+
+
+def _challenge_stage_ms(r):
+    ev = r['timing']['events']
+    return {'st_mot_file_round': ev[0].elapsed_time(ev[1]), 'st_mot_challenge_preprocess': ev[1].elapsed_time(ev[2])}
+
+
+def motchallenge_keep_masks(gts, preds, benchmark='MOT17', device=None, videos=None, timing=False):
+    """protocol='trackeval' ahead of the scorers, for every sequence (or sweep member) in ONE call: the rows are
+    uploaded once, st_mot_file_round turns them into what a reader of the MOTChallenge files gets
+    (metrics.motchallenge_file_rows, the specification), st_mot_challenge_preprocess applies TrackEval's preprocessing
+    to those (metrics.motchallenge_preprocess), and the keep bytes come back with one wait and one copy.
+    gts / preds: lists of row arrays, gt (n, 6 .. 9) = (frame, id, x, y, w, h[, conf, class, visibility]; conf 1 and
+    class 1 where absent), pred (m, 6 .. 7), rows in any order.  Returns one (gt_keep (n,), pred_keep (m,)) pair of
+    boolean arrays per sequence, over the rows as they were passed.  videos: the names for error messages.
+    timing: returns (masks, dict) with the stages' device time (HIP events) and the host clock of the call's parts."""
+    r = _challenge_device(gts, preds, benchmark, device, videos, timing)
+    out, g0, p0 = [], 0, 0
+    for og, op_ in r['orders']:
+        a, b = np.zeros(len(og), bool), np.zeros(len(op_), bool)
+        a[og] = r['gt_keep'][g0:g0 + len(og)] != 0
+        b[op_] = r['pred_keep'][p0:p0 + len(op_)] != 0
+        g0, p0 = g0 + len(og), p0 + len(op_)
+        out.append((a, b))
+    if timing:
+        t = r['timing']
+        t_end = time.perf_counter()
+        return out, dict(stages_ms=_challenge_stage_ms(r), host_prepare_s=t['host_prepare_s'],
+                         device_and_copies_s=t['device_and_copies_s'], host_finish_s=t_end - t['t_back'])
+    return out
+
+
+def evaluate_motchallenge(gts, preds, benchmark='MOT17', iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None,
+                          videos=None, timing=False):
+    """MOTDroneMetrics(protocol='trackeval', backend='device'): the sequences through _challenge_device, then the rows
+    it keeps through the four scoring stages (evaluate_packed).  The scorers' tables come from the frame and id columns,
+    truncated on the host; the rounded boxes are gathered on the device and never visit the host.  Returns one dict per
+    sequence as evaluate_packed does; timing: (results, dict) with both parts' figures."""
+    r = _challenge_device(gts, preds, benchmark, device, videos, timing)
+    names = r['videos']
+    keys = names if sorted(set(names)) == names else list(range(len(names)))      # pack_sequences sorts its videos
+    kept, by_video = [], ({}, {})
+    for kind, keep in enumerate((r['gt_keep'], r['pred_keep'])):
+        kept.append(np.nonzero(keep)[0])
+        r0 = 0
+        for s, rows in enumerate(r['sorted_rows'][kind]):
+            m = keep[r0:r0 + len(rows)] != 0
+            head = np.zeros((int(m.sum()), 6))
+            head[:, 0], head[:, 1] = r['frames_of'][s][kind][m], np.trunc(rows[m, 1])
+            by_video[kind][keys[s]] = head
+            r0 += len(rows)
+    packed = pack_sequences(*by_video)
+    dev = r['device']
+    boxes = [src[torch.from_numpy(idx).to(dev)][:, 2:6].contiguous() for src, idx in zip((r['gt_file'], r['pred_file']), kept)]
+    res = evaluate_packed(packed, iou_thr, metrics, dev, timing=timing, device_boxes=boxes)
+    if timing:
+        res, t = res
+        t['challenge'] = dict(stages_ms=_challenge_stage_ms(r), host_prepare_s=r['timing']['host_prepare_s'],
+                              device_and_copies_s=r['timing']['device_and_copies_s'])
+        return res, t
+    return res
+
+
 def image_space_rows(frames, rows, ids, n):
     """Tracker outputs on the host - frames (T, B), rows (T, B, M, row floats), ids (T, B, M), n (T, B), views allowed -
     -> one (R, 6) fp64 array per sequence: (frame, id, x, y, w, h) of every output row, in step order, in IMAGE
@@ -493,7 +733,7 @@ class TrackCollector:
 
 
 def evaluate_sweep(predictions, gt, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None, backend='device',
-                   postprocess=None):
+                   postprocess=None, protocol='rows', benchmark='MOT17'):
     """Scores the B prediction sets of a batched tracker run (a TrackCollector, or a list of B row arrays) against one
     ground-truth row array (shared) or a list of B of them.  Returns B dicts as evaluate_packed does.  A collector's
     rows are scaled back to image space (TrackCollector.prediction_rows), so the ground truth is the image-space one;
@@ -501,7 +741,15 @@ def evaluate_sweep(predictions, gt, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Iden
     backend='host' scores the same rows with metrics.clear_identity / metrics.hota (the reference of the tests).
     postprocess: any entry with forward_many(list of row arrays) -> list - a tracklets.InterpolateTracklets, an
     aflink.AppearanceFreeLink - or a list of them, applied in order over the B prediction sets before they are scored,
-    each through one forward_many call on its own backend; 6-column rows (a collector's) get the score 1.0 first."""
+    each through one forward_many call on its own backend; 6-column rows (a collector's) get the score 1.0 first.
+    protocol='trackeval': what MOTDroneMetrics(protocol='trackeval', benchmark=...) scores - the MOTChallenge files'
+    values after TrackEval's preprocessing (metrics.motchallenge_file_rows / motchallenge_preprocess; on the device
+    evaluate_motchallenge, one call for all B members).  The ground truth may then carry 9 columns (conf, class,
+    visibility); without them every row has conf 1, class 1."""
+    from . import metrics as M
+    if protocol not in M.PROTOCOLS:
+        raise ValueError(f'evaluate_sweep: protocol must be one of {M.PROTOCOLS}, got {protocol!r}')
+    M.motchallenge_distractors(benchmark)
     preds = predictions.prediction_rows() if isinstance(predictions, TrackCollector) else list(predictions)
     if postprocess is not None:
         preds = [np.asarray(p, dtype=np.float64).reshape(-1, np.shape(p)[-1] if np.size(p) else 7) for p in preds]
@@ -512,9 +760,14 @@ def evaluate_sweep(predictions, gt, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Iden
     if len(gts) != len(preds):
         raise ValueError(f'evaluate_sweep: {len(preds)} prediction sets against {len(gts)} ground-truth sets')
     if backend == 'host':
-        from . import metrics as M
+        if protocol == 'trackeval':
+            ks = list(range(len(preds)))
+            g_, p_ = M.motchallenge_scored_rows(dict(zip(ks, gts)), dict(zip(ks, preds)), ks, benchmark)
+            gts, preds = [g_[k] for k in ks], [p_[k] for k in ks]
         return [dict(clear_identity=M.clear_identity(g, p, iou_thr), hota=M.hota(g, p) if 'HOTA' in metrics else None)
                 for g, p in zip(gts, preds)]
     if backend != 'device':
         raise ValueError(f"evaluate_sweep: backend must be 'host' or 'device', got {backend!r}")
+    if protocol == 'trackeval':
+        return evaluate_motchallenge(gts, preds, benchmark, iou_thr, metrics, device)
     return evaluate_packed(pack_sequences(gts, preds), iou_thr, metrics, device)

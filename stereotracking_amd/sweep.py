@@ -184,11 +184,14 @@ class SweepResult:
         frames = np.tile(np.arange(F)[:, None], (1, B))                                   # (F, B)
         return image_space_rows(frames, self.rows.transpose(1, 0, 2, 3), self.ids.transpose(1, 0, 2), self.n.T)
 
-    def scores(self, gt_by_video, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), backend='device', postprocess=None):
+    def scores(self, gt_by_video, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), backend='device', postprocess=None,
+               protocol='rows', benchmark='MOT17'):
         """gt_by_video: the V ground-truth row arrays (frame, id, x, y, w, h, ...), image space, frame = the frame's
         index in the video (prediction_rows).  -> one dict per option set: its V videos' results combined by metrics.combine_videos (the
         rule of MOTDroneMetrics), plus 'status' = the set's V member codes.  An option set with an overflowed member is
-        NOT scored: its dict holds only 'status' and 'overflowed' = True, and a warning names the members."""
+        NOT scored: its dict holds only 'status' and 'overflowed' = True, and a warning names the members.
+        protocol / benchmark: as MOTDroneMetrics' (mot_eval.evaluate_sweep); with 'trackeval' the ground truth may carry
+        the conf, class and visibility columns."""
         from . import metrics as M
         from .mot_eval import evaluate_sweep
         gts = list(gt_by_video)
@@ -201,7 +204,7 @@ class SweepResult:
         good = [k for k in range(self.K) if not self.status[k * self.V:(k + 1) * self.V].any()]
         preds = self.prediction_rows()
         res = evaluate_sweep([preds[k * self.V + v] for k in good for v in range(self.V)], gts * len(good), iou_thr,
-                             metrics, self.device, backend, postprocess) if good else []
+                             metrics, self.device, backend, postprocess, protocol, benchmark) if good else []
         out = [dict(status=self.status[k * self.V:(k + 1) * self.V].tolist(), overflowed=True) for k in range(self.K)]
         for i, k in enumerate(good):
             r = res[i * self.V:(i + 1) * self.V]
