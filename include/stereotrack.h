@@ -202,6 +202,22 @@ int st_pack_raw_frames(const unsigned char* const* frames_u8_dev_ptrs_host, int 
  * 1- / 2- / 4-byte elements (uint8 masks, uint16 PNG codes, fp32 maps: the sampling commutes with code / 16). */
 int st_resize_planes(const void* in_dev, int P, int h, int w, int interleaved, void* out_dev, int h2, int w2,
                      int elem_bytes, int bilinear, st_stream_t stream);
+/* StereoRectify (new; the reference's AirSim pairs arrive rectified): undistort + rectify F <= 32 raw frames through
+ * fixed-point maps in ONE launch (csrc/rectify.hip).  src_dev_ptrs_host = HOST array of F device pointers (they travel
+ * in the kernel arguments), each a contiguous planar (P, h, w) frame, P in {1, 3}; maps_dev = M maps [M][h2][w2][2]
+ * int32 (qx, qy) in 1/32 px (stereotracking_amd/rectify.py builds them: initUndistortRectifyMap restated, 8-byte
+ * aligned); map_index_host[f] in [0, M) selects frame f's map (left / right of a pair in one launch).  The results go
+ * to dst_dev_ptrs_host (HOST array of F device pointers) or to dst_block_dev (one contiguous (F, P, h2, w2) block);
+ * exactly one of the two is non-NULL.  Rule (exact integers, identical on host and device): x0 = qx >> 5, a = qx & 31,
+ * y0 = qy >> 5, b = qy & 31;  bilinear = 1 (elem_bytes 1 only):
+ *   out = ((32-a)(32-b) p00 + a(32-b) p01 + (32-a)b p10 + ab p11 + 512) >> 10
+ * with a tap outside the raw image = border and a tap of weight 0 NEVER READ - cv2.remap's 8-bit INTER_LINEAR on
+ * CV_16SC2 maps (cv2 un-vendored: published algorithm, parity unpinned);  bilinear = 0 (elem_bytes 1, 2 or 4): the
+ * element at ((qx + 16) >> 5, (qy + 16) >> 5), outside the image `border` (1-byte elements) or 0.  Any h, w, h2, w2;
+ * no workspace; nothing outside the outputs is written, nothing outside the frames and maps is read. */
+int st_rectify_remap(const void* const* src_dev_ptrs_host, int F, int P, int h, int w, const int* maps_dev, int M,
+                     const int* map_index_host, void* const* dst_dev_ptrs_host, void* dst_block_dev, int h2, int w2,
+                     int elem_bytes, int bilinear, int border, st_stream_t stream);
 
 /* SPP: out[..., 0:C]=x, [C:2C]=maxpool5, [2C:3C]=maxpool9, [3C:4C]=maxpool13
  * (stride 1, same pad, -inf padding).  x may alias out channels [0,C).

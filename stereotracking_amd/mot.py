@@ -32,6 +32,7 @@ from .motion import KalmanFilter  # noqa: F401  (registers the motion model)
 from . import detectors  # noqa: F401  (registers detector / backbone / neck / head)
 from . import stereo as _stereo  # noqa: F401  (registers StereoCostVolume)
 from . import sgbm as _sgbm  # noqa: F401  (registers StereoSGBM)
+from . import rectify as _rectify  # noqa: F401  (registers StereoRectify)
 from . import coco_metric as _coco_metric  # noqa: F401  (registers CocoMetric in METRICS)
 from . import kitti_metrics as _kitti_metrics  # noqa: F401  (registers MOTKittiMetrics in METRICS)
 from . import tracklets as _tracklets  # noqa: F401  (registers InterpolateTracklets in TASK_UTILS)
@@ -252,12 +253,15 @@ class OCSORT_Disparity(nn.Module):
     writer; 'input': moved back to the device of the inputs like the reference's tensors) and `depth_extraction`
     (the per-box depth estimator of the detections, the track boxes and the gt depth alike: 'reference', or
     'truncated_mean' / 'mean' / 'median' / 'center', the alternatives the reference selects by decorating
-    extract_depth, mmtrack/models/mot/depth_extraction_comparison.py)."""
+    extract_depth, mmtrack/models/mot/depth_extraction_comparison.py) and `rectify` (a StereoRectify config for RAW,
+    unrectified stereo pairs: each chunk's uint8 left / right frames are undistorted + rectified on the device in one
+    launch before the stem and the stereo module read them; results are then in rectified-left coordinates, see
+    StereoRectify.to_raw_boxes; baseline='calibration' / focal_length='calibration' take the rectifier's values)."""
 
     def __init__(self, detector=None, tracker=None, motion=None, data_preprocessor=None, init_cfg=None,
                  baseline=0.25, focal_length=640, stereo=None, dense_batch=8, inflight=3, max_det=1000,
                  results_device='cpu', autotune=True, tuning_cache=None, results_csv=None, split_bf16=None,
-                 queue_depth=1, depth_extraction='reference'):
+                 queue_depth=1, depth_extraction='reference', rectify=None):
         super().__init__()
         depth_method_code(depth_extraction)     # ValueError for an unknown estimator, before anything is built
         self.depth_extraction = depth_extraction
@@ -265,6 +269,32 @@ class OCSORT_Disparity(nn.Module):
         self.detector = MODELS.build(detector) if detector is not None else None
         self.motion = TASK_UTILS.build(motion) if motion is not None else None
         self.tracker = MODELS.build(tracker) if tracker is not None else None
+        # raw (distorted, unrectified) pairs: a StereoRectify config; each chunk's left / right frames are rectified on
+        # the device in one launch (shell_inputs.chunk_inputs).  None: the inputs are rectified pairs, as ever
+        if isinstance(rectify, (list, tuple)):
+            raise NotImplementedError('rectify takes ONE StereoRectify calibration; a list of calibrations (one per '
+                                      'stream) is not implemented')
+        self.rectify = MODELS.build(rectify) if isinstance(rectify, dict) else rectify
+        if self.rectify is not None:
+            if not isinstance(self.rectify, _rectify.StereoRectify):
+                raise TypeError('rectify must be a StereoRectify config or instance')
+            if self.rectify.out_size != self.rectify.size:
+                raise NotImplementedError(
+                    f'rectify: out_size {self.rectify.out_size} != size {self.rectify.size} is not wired into the shell '
+                    f'(ori_shape, the detector plan and the box rescale follow the raw frame size); st_rectify_remap '
+                    f'itself supports it (StereoRectify.remap)')
+            if getattr(self.tracker, 'with_cmc', False) or getattr(self.tracker, 'cmc_cfg', None) is not None:
+                raise NotImplementedError('rectify with camera-motion compensation is not implemented: cmc estimates '
+                                          'its warps on the raw left frames')
+        for name, given in (('baseline', baseline), ('focal_length', focal_length)):
+            if isinstance(given, str):
+                if given != 'calibration' or self.rectify is None:
+                    raise ValueError(f"{name}='calibration' takes the value from the `rectify` calibration; got "
+                                     f"{name}={given!r} with rectify={'set' if self.rectify is not None else None}")
+        if baseline == 'calibration':
+            baseline = self.rectify.baseline
+        if focal_length == 'calibration':
+            focal_length = self.rectify.focal_length
         self.baseline, self.focal_length = baseline, focal_length
         if (stereo is not None and stereo.get('full_res') and 'feat_channels' not in stereo and self.detector is not None):
             # the full-resolution mode's reduce conv reads the detector's stage-1 features: make_divisible(128, widen)

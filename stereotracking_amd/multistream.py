@@ -44,11 +44,15 @@ class StreamOverflow(RuntimeError):
 class MultiStreamTracker:
     """dict(type='MultiStreamTracker', model=<OCSORT_Disparity config or built model>, streams=S, max_tracks=128,
     max_dets=None).  Owns no weights: detector, stereo module, thresholds, baseline / focal_length, depth_extraction,
-    dense_batch, inflight, queue_depth, max_det, results_device and the tracker options are the wrapped model's.
+    dense_batch, inflight, queue_depth, max_det, results_device, the `rectify` calibration (shared by all streams) and
+    the tracker options are the wrapped model's.
     max_tracks / max_dets: capacities per stream of the device tracker (max_dets=None: the model's max_det; EVERY
     detection the detector keeps is a row of the tracker's input, as in the host shell)."""
 
     def __init__(self, model, streams, max_tracks=128, max_dets=None):
+        if isinstance(getattr(model, 'get', lambda k: None)('rectify'), (list, tuple)):
+            raise NotImplementedError('MultiStreamTracker: the streams share the wrapped model\'s ONE `rectify` calibration; '
+                                      'a list of calibrations (one per stream) is not implemented')
         if isinstance(model, dict):
             model = MODELS.build(model)
         if not all(hasattr(model, a) for a in ('dense_runner', '_box_depth', 'tracker', 'max_det', 'dense_batch')):

@@ -403,6 +403,13 @@ class InflightPipelines:
                 p.det.set_tuning(first.det.get_tuning())
                 p.stereo_module.variant = first.stereo_module.variant
 
+    def next_stream(self, device):
+        """The stream of the context the NEXT submit() runs on: work that produces that batch's inputs may be enqueued
+        there directly instead of on the caller's stream."""
+        if self.streams is None:
+            self.streams = [torch.cuda.Stream(device=device) for _ in self.pipes]
+        return self.streams[self._next % len(self.pipes)]
+
     def submit(self, img, right=None, disp_postp=None, post=None):
         """Enqueue one batch on the next context's stream (after everything already enqueued on the caller's
         current stream, where the inputs were produced).  `post(out)` runs under that stream too."""

@@ -97,6 +97,8 @@ def plan_inputs(model, inputs, data_samples, who):
     """Validate one call's preprocessed inputs; nothing is launched.  -> (img, second input of the dense plan: the right
     images when `stereo`, else disp_postp, gt depth maps or None, stereo, the frames' ori_shape).  `who`: the entry
     point's name in the refusal of host tensors."""
+    if getattr(model, 'rectify', None) is not None:
+        check_rectify_inputs(model.rectify, inputs)
     img, disp_postp = _unwrap(inputs['img'], 'img'), inputs.get('disp_postp')
     assert len(data_samples) == len(img)
     if img.device.type != 'cuda':
@@ -124,6 +126,34 @@ def plan_inputs(model, inputs, data_samples, who):
     return img, second, gt, stereo, ori
 
 
+def check_rectify_inputs(rect, inputs):
+    """What a shell with `rectify` set takes: the stereo-input configuration (img + right) as raw uint8 frames of the
+    calibration's size.  Everything else is refused here, before anything is launched."""
+    if inputs.get('disp_postp') is not None:
+        raise NotImplementedError("rectify is set but the inputs carry 'disp_postp': a disparity map is already in "
+                                  "rectified coordinates and the raw image beside it is not; rectify applies to the "
+                                  "stereo-input configuration ('img' + 'right')")
+    for name in ('img', 'right'):
+        t = inputs.get(name)
+        if t is None:
+            raise KeyError(f"rectify is set: the inputs need 'img' and 'right' (raw uint8 frames), '{name}' is missing")
+        if not isinstance(t, RawFrames):
+            raise NotImplementedError(f"rectify remaps raw uint8 frames (cv2.remap's 8-bit rule); '{name}' arrived as a "
+                                      f"{getattr(t, 'dtype', type(t).__name__)} tensor - pass uint8 frames, or rectify "
+                                      f"fp32 images before the call")
+        if tuple(t.hw) != tuple(rect.size):
+            raise ValueError(f"rectify: '{name}' frames are {tuple(t.hw)}, the calibration is for {tuple(rect.size)}")
+    if len(inputs['img']) != len(inputs['right']):
+        raise ValueError(f"rectify: {len(inputs['img'])} left frames, {len(inputs['right'])} right frames")
+
+
+def rectified_chunk(rect, img, second, s, e):
+    """Frames [s, e) of a raw stereo call, rectified: left and right frames in ONE st_rectify_remap launch on the current
+    stream -> two RawFrames of e - s frames (views of one uint8 block), read by the raw stem and StereoSGBM unchanged."""
+    left, right = rect.rectify_pairs(img.frames[s:e], second.frames[s:e])
+    return RawFrames(left, img.pad_hw, img.pad_value), RawFrames(right, second.pad_hw, second.pad_value)
+
+
 def padded(t, s, e, B):
     """frames [s, e) of a call's input as a (B, C, H, W) fp32 batch."""
     if isinstance(t, RawFrames):
@@ -135,7 +165,22 @@ def padded(t, s, e, B):
 
 
 def chunk_inputs(model, img, second, stereo, s, e, B, runner):
-    """Frames [s, e) of a planned call -> the two inputs (a, b) of `runner.submit`."""
+    """Frames [s, e) of a planned call -> the two inputs (a, b) of `runner.submit`.  With model.rectify set the chunk's
+    raw pairs are rectified first, under the stream of the context the chunk is submitted to (so the pass is part of
+    that context's pipelined work and overlaps the dense work of the other contexts)."""
+    rect = getattr(model, 'rectify', None)
+    if rect is None:
+        return _chunk_inputs(model, img, second, stereo, s, e, B, runner)
+    ctx = runner.next_stream(img.device)
+    ctx.wait_stream(torch.cuda.current_stream(img.device))       # the raw frames were uploaded on the caller's stream
+    for f in img.frames[s:e] + second.frames[s:e]:
+        f.record_stream(ctx)
+    with torch.cuda.stream(ctx):
+        img, second = rectified_chunk(rect, img, second, s, e)
+        return _chunk_inputs(model, img, second, stereo, 0, e - s, B, runner)
+
+
+def _chunk_inputs(model, img, second, stereo, s, e, B, runner):
     a = b = None
     if model.raw_stem and isinstance(img, RawFrames):
         if stereo and isinstance(second, RawFrames):
