@@ -1297,6 +1297,58 @@ size_t st_mot_challenge_workspace_bytes(const StMotChallengeArgs* args);
 int st_mot_challenge_preprocess(const StMotChallengeArgs* args, st_stream_t stream);
 
 /* ----------------------------------------------------------------------
+ * 22. Dense stereo evaluation (stereo_eval.stereo_error_stats, StereoMetric, OCSORT_Disparity(stereo_eval=...)),
+ *     csrc/stereo_eval.hip.  NEW, no reference function: the definitions below are the specification, their executable
+ *     form is tests/stereo_eval_ref.py (numpy float32 / float64, operation by operation).
+ *   inputs   pred: plane 0 of an (N, C, H, W) fp32 disparity map (pixels), image n at pred_dev + n * pred_img_pitch
+ *            floats, rows of W floats; gt: plane 0 of an (N, Cg, H, W) fp32 map, gt_img_pitch likewise, metres
+ *            (ST_STEREO_GT_DEPTH) or pixels (ST_STEREO_GT_DISP).  extent (N, 2) int32 = (h_n, w_n), clamped to (H, W):
+ *            rows >= h_n and columns >= w_n are padding and are NOT read, nor is any other plane.  boxes
+ *            (N, max_boxes, 4) fp32 xyxy and box_counts (N,) int32 (clamped to 0..max_boxes; rows at or beyond the count
+ *            are not read); max_boxes == 0: no boxes, both pointers may be NULL.  bf = baseline * focal length.
+ *   pixel    all fp32, unfused, IEEE division.  depth: gz = g, gd = bf / gz; disp: gd = g, gz = bf / gd.
+ *            gt-valid: g finite, g > 0, depth_edges[0] < gz <= depth_edges[K]; depth bin b: depth_edges[b] < gz <=
+ *            depth_edges[b + 1].  pred-valid: p finite, p > 0; pz = bf / p.  region 1 iff a counted box row has
+ *            x1 <= (float)x < x2 and y1 <= (float)y < y2, else 0.  On pixels valid both ways: e = |p - gd|;
+ *            bad_t: e > bad_thresholds[t]; d1: e > 3 && e > 0.05f * gd; r = max(pz / gz, gz / pz), delta_k: r < 1.25^k
+ *            (k = 1, 2, 3); histogram bin e * 16 >= 511 ? 511 : (int)(e * 16); fp64 dz = (double)pz - (double)gz.
+ *   outputs  per cell (n, region, bin), region-major: counts (N, 2, K, T + 6) int64 = n_gt, n_both, n_bad[T], n_d1,
+ *            n_delta[3]; sums (N, 2, K, 5) fp64 = sum e, e^2, |dz| / gz, dz^2 / gz, dz^2 (every term formed in double
+ *            from the fp32 values); hist (N, 2, K, 512) int64.  Every cell is defined by the call, whatever the buffers
+ *            and the workspace held.  Integers are exact; the fp64 sums use NO floating-point atomics (fixed pixel range
+ *            per workgroup, fixed reduction tree, one partial per cell in the workspace, a second launch adds the
+ *            partials in index order): two calls on the same inputs return the same bytes.
+ *   workspace  caller-owned device memory, 8-byte aligned, st_stereo_eval_workspace_bytes(args) bytes (0: invalid
+ *            arguments), its size in args->workspace_bytes.  Enqueued on `stream` (one memset of hist, two launches), no
+ *            host wait, no allocation.  A call that returns non-zero has launched nothing.
+ * ---------------------------------------------------------------------- */
+#define ST_STEREO_EVAL_MAX_BINS 8
+#define ST_STEREO_EVAL_MAX_THRESHOLDS 6
+#define ST_STEREO_EVAL_HIST_BINS 512
+#define ST_STEREO_EVAL_NUM_SUMS 5
+#define ST_STEREO_EVAL_MAX_BOXES 256
+#define ST_STEREO_GT_DEPTH 0
+#define ST_STEREO_GT_DISP 1
+typedef struct StStereoEvalArgs {
+  int struct_size;              /* sizeof(StStereoEvalArgs) */
+  int N, H, W;
+  int gt_kind;                  /* ST_STEREO_GT_DEPTH / ST_STEREO_GT_DISP */
+  int num_bins;                 /* K, 1 .. ST_STEREO_EVAL_MAX_BINS */
+  int num_thresholds;           /* T, 1 .. ST_STEREO_EVAL_MAX_THRESHOLDS */
+  int max_boxes;                /* M, 0 .. ST_STEREO_EVAL_MAX_BOXES */
+  size_t pred_img_pitch;        /* floats between images of pred (>= H * W) */
+  size_t gt_img_pitch;          /* floats between images of gt */
+  size_t workspace_bytes;
+  float bf;
+  float depth_edges[ST_STEREO_EVAL_MAX_BINS + 1];     /* K + 1 used, strictly ascending */
+  float bad_thresholds[ST_STEREO_EVAL_MAX_THRESHOLDS]; /* T used */
+} StStereoEvalArgs;
+size_t st_stereo_eval_workspace_bytes(const StStereoEvalArgs* args);
+int st_stereo_eval(const StStereoEvalArgs* args, const float* pred_dev, const float* gt_dev, const int32_t* extent_dev,
+                   const float* boxes_dev, const int32_t* box_counts_dev, int64_t* counts_dev, double* sums_dev,
+                   int64_t* hist_dev, void* workspace_dev, st_stream_t stream);
+
+/* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).
  * Replaces the OpenCV PNG decode behind mmcv.imfrombytes(..., flag='unchanged') that the reference's loaders call
  * (mmtrack/datasets/transforms/loading_disparity.py:74-75 uint16 disparity, :213-215 uint16 depth; mmcv's

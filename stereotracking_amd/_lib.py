@@ -158,6 +158,13 @@ class StMotChallengeArgs(C.Structure):
         [('ws_bytes', C.c_size_t)] + [(n, C.c_void_p) for n in ('gt_keep', 'pred_keep', 'status')]
 
 
+class StStereoEvalArgs(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('struct_size', 'N', 'H', 'W', 'gt_kind', 'num_bins', 'num_thresholds',
+                                       'max_boxes')] + \
+        [(n, C.c_size_t) for n in ('pred_img_pitch', 'gt_img_pitch', 'workspace_bytes')] + \
+        [('bf', C.c_float), ('depth_edges', C.c_float * 9), ('bad_thresholds', C.c_float * 6)]
+
+
 class StTrackletArgs(C.Structure):
     _fields_ = [(n, C.c_int) for n in ('struct_size', 'num_rows', 'num_out_rows', 'num_tracks', 'first', 'count',
                                        'num_groups', 'max_rows')] + \
@@ -335,6 +342,8 @@ _PROTOS = {
     'st_mot_file_round': (_i, [_vp, _vp, C.c_longlong, _i, C.POINTER(C.c_int), _vp, _vp]),
     'st_mot_challenge_workspace_bytes': (_sz, [C.POINTER(StMotChallengeArgs)]),
     'st_mot_challenge_preprocess': (_i, [C.POINTER(StMotChallengeArgs), _vp]),
+    'st_stereo_eval_workspace_bytes': (_sz, [C.POINTER(StStereoEvalArgs)]),
+    'st_stereo_eval': (_i, [C.POINTER(StStereoEvalArgs), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'st_tracklet_max_rows': (_i, []),
     'st_tracklet_gsi_workspace_bytes': (_sz, [C.POINTER(StTrackletArgs)]),
     'st_tracklet_interpolate': (_i, [C.POINTER(StTrackletArgs), _vp]),

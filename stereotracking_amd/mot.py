@@ -37,6 +37,7 @@ from . import coco_metric as _coco_metric  # noqa: F401  (registers CocoMetric i
 from . import kitti_metrics as _kitti_metrics  # noqa: F401  (registers MOTKittiMetrics in METRICS)
 from . import tracklets as _tracklets  # noqa: F401  (registers InterpolateTracklets in TASK_UTILS)
 from . import camera_motion as _camera_motion  # noqa: F401  (registers CameraMotionCompensation in TASK_UTILS)
+from . import stereo_eval as _stereo_eval  # noqa: F401  (registers StereoMetric in METRICS)
 
 
 def stack_batch(tensors, pad_size_divisor=0, pad_value=0):
@@ -253,7 +254,10 @@ class OCSORT_Disparity(nn.Module):
     writer; 'input': moved back to the device of the inputs like the reference's tensors) and `depth_extraction`
     (the per-box depth estimator of the detections, the track boxes and the gt depth alike: 'reference', or
     'truncated_mean' / 'mean' / 'median' / 'center', the alternatives the reference selects by decorating
-    extract_depth, mmtrack/models/mot/depth_extraction_comparison.py) and `rectify` (a StereoRectify config for RAW,
+    extract_depth, mmtrack/models/mot/depth_extraction_comparison.py), `stereo_eval` (None, or
+    dict(depth_edges=..., bad_thresholds=..., boxes='gt' | None): every chunk's disparity is scored against the call's
+    `depth_postp` maps in one st_stereo_eval launch beside the track-box depth, and every sample's metainfo gets
+    `stereo_stats`, a one-frame stereo_eval.StereoStats) and `rectify` (a StereoRectify config for RAW,
     unrectified stereo pairs: each chunk's uint8 left / right frames are undistorted + rectified on the device in one
     launch before the stem and the stereo module read them; results are then in rectified-left coordinates, see
     StereoRectify.to_raw_boxes; baseline='calibration' / focal_length='calibration' take the rectifier's values)."""
@@ -261,9 +265,10 @@ class OCSORT_Disparity(nn.Module):
     def __init__(self, detector=None, tracker=None, motion=None, data_preprocessor=None, init_cfg=None,
                  baseline=0.25, focal_length=640, stereo=None, dense_batch=8, inflight=3, max_det=1000,
                  results_device='cpu', autotune=True, tuning_cache=None, results_csv=None, split_bf16=None,
-                 queue_depth=1, depth_extraction='reference', rectify=None):
+                 queue_depth=1, depth_extraction='reference', rectify=None, stereo_eval=None):
         super().__init__()
         depth_method_code(depth_extraction)     # ValueError for an unknown estimator, before anything is built
+        self.stereo_eval = self._stereo_eval_options(stereo_eval)      # None: the dense evaluator is off
         self.depth_extraction = depth_extraction
         self.data_preprocessor = MODELS.build(data_preprocessor) if data_preprocessor is not None else None
         self.detector = MODELS.build(detector) if detector is not None else None
@@ -333,6 +338,54 @@ class OCSORT_Disparity(nn.Module):
         self._dense = {}          # (batch, ori_h, ori_w, stereo, depth_extraction) -> [InflightPipelines, weights version]
         self._staging = {}        # name -> pinned host buffer (grow-only): no pinned allocation on the per-chunk path
         self.timings = dict(frames=0, tracker_s=0.0, host_s=0.0, wait_s=0.0, pre_s=0.0, tail_s=0.0, submit_s=0.0, depth_s=0.0)   # cumulative host-side costs
+
+    @staticmethod
+    def _stereo_eval_options(cfg):
+        if cfg is None:
+            return None
+        if not isinstance(cfg, dict):
+            raise TypeError(f'stereo_eval must be None or a dict, got {type(cfg).__name__}')
+        unknown = set(cfg) - {'depth_edges', 'bad_thresholds', 'boxes'}
+        if unknown:
+            raise ValueError(f'stereo_eval: unknown keys {sorted(unknown)} (depth_edges, bad_thresholds, boxes)')
+        if cfg.get('boxes') not in ('gt', None):
+            raise ValueError(f"stereo_eval: boxes must be 'gt' or None, got {cfg.get('boxes')!r}")
+        edges, taus = _stereo_eval.check_options(cfg.get('depth_edges'), cfg.get('bad_thresholds'))
+        return dict(depth_edges=edges, bad_thresholds=taus, boxes=cfg.get('boxes'))
+
+    def _stereo_eval_launch(self, st, job, ci, s, e, B):
+        """Under the side stream, beside the track-box depth launch: ONE st_stereo_eval call of the chunk's disparity
+        against its depth maps; the accumulators start their way to a page-locked buffer that finalize() reads."""
+        opt, samples, dev = self.stereo_eval, st['data_samples'], st['dev']
+        disp = job['disp']
+        H, W = int(disp.shape[-2]), int(disp.shape[-1])
+        idx = list(range(s, e)) + [e - 1] * (B - (e - s))      # the padding frames repeat the last one (dropped later)
+        ext = []
+        for n in idx:
+            shape = samples[n].metainfo.get('img_shape', (H, W))
+            ext.append((min(int(shape[0]), H), min(int(shape[1]), W)))
+        boxes = counts = None
+        if opt['boxes'] == 'gt':
+            rows = []
+            for n in idx:
+                gi = samples[n].get('gt_instances')
+                rows.append(gi.bboxes.detach().float().cpu().reshape(-1, 4) if gi is not None and 'bboxes' in gi
+                            else torch.zeros(0, 4))
+            M = max(len(r) for r in rows)
+            if M > 0:
+                hb = torch.zeros(B, M, 4)
+                for i, r in enumerate(rows):
+                    hb[i, :len(r)] = r
+                boxes = hb.to(dev)
+                counts = torch.tensor([len(r) for r in rows], dtype=torch.int32).to(dev)
+        out = _stereo_eval.launch_stereo_eval(
+            disp, shell_inputs.padded(st['gt'], s, e, B), 'depth',
+            _stereo_eval.bf_float32(self.baseline, self.focal_length),
+            torch.tensor(ext, dtype=torch.int32).to(dev), boxes, counts, opt['depth_edges'], opt['bad_thresholds'],
+            lib=self.lib)
+        host = self._pinned(('stereo_stats', id(st['runner']), ci), out.shape, out.dtype)   # read at the end of the call
+        host.copy_(out, non_blocking=True)
+        return host
 
     # ---- reference plumbing (mot/base.py:68-113) -----------------------------------------------------
     def init_weights(self):
@@ -484,6 +537,8 @@ class OCSORT_Disparity(nn.Module):
         N = len(img)
         B = min(self.dense_batch, N)      # a call with fewer frames than dense_batch gets a plan of its own size
         runner = self.dense_runner(ori, stereo, B)
+        if self.stereo_eval is not None and gt is None:
+            raise KeyError("stereo_eval is set: the inputs need 'depth_postp' (the ground-truth depth maps)")
         return dict(img=img, second=second, gt=gt, stereo=stereo, N=N, B=B, runner=runner, dev=img.device,
                     data_samples=data_samples, kwargs=kwargs, jobs={}, submitted=0,
                     chunks=[(s, min(s + B, N)) for s in range(0, N, B)])
@@ -604,7 +659,14 @@ class OCSORT_Disparity(nn.Module):
         outs, pending = [None] * N, []
         t_tail0 = time.perf_counter()
         def finalize(entry):   # depth of the unscaled track boxes has arrived: complete the chunk's samples
-            s, e, tracks_of, dh, _ev2, _keep = entry
+            s, e, tracks_of, dh, _ev2, _keep, sev = entry
+            if sev is not None:    # the chunk's dense-evaluation accumulators: one StereoStats per REAL frame
+                opt = self.stereo_eval
+                cnt, sm, hs = _stereo_eval.unpack(sev, B, len(opt['depth_edges']) - 1, len(opt['bad_thresholds']))
+                for i in range(e - s):
+                    data_samples[s + i].set_metainfo(dict(stereo_stats=_stereo_eval.StereoStats(
+                        cnt[i:i + 1].numpy().copy(), sm[i:i + 1].numpy().copy(), hs[i:i + 1].numpy().copy(),
+                        opt['depth_edges'], opt['bad_thresholds'])))
             for i, tracks in enumerate(tracks_of):
                 k = len(tracks)
                 tracks['depth'] = dh[0, i, :k].clone()
@@ -705,12 +767,13 @@ class OCSORT_Disparity(nn.Module):
                     cols.append(self._box_depth(shell_inputs.padded(gt, s, e, B), tbd, tcd, -1.0, 1.0)[0])
                 dh = self._pinned(('track_depth', id(runner), ci), (len(cols), B, mt))   # read at the end of the call
                 dh.copy_(torch.stack(cols), non_blocking=True)
+                sev = self._stereo_eval_launch(st, job, ci, s, e, B) if self.stereo_eval is not None else None
                 ev2 = torch.cuda.Event()
                 ev2.record(stream)
                 self._staging[slot_key] = ev2      # recorded after the copies that read tb / tc
                 if job['disp_slot'] is not None:   # ... and after the last read of this disparity buffer
                     runner.pipes[job['ctx']].disp_guard[job['disp_slot']] = ev2
-            pending.append((s, e, tracks_of, dh, ev2, (tbd, tcd)))
+            pending.append((s, e, tracks_of, dh, ev2, (tbd, tcd), sev))
             self.timings['depth_s'] += time.perf_counter() - td
             while pending and pending[0][4].query():       # earlier chunks whose track depth has landed: complete
                 finalize(pending.pop(0))                   # them now, while the device works on the next chunks

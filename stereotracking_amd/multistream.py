@@ -68,6 +68,10 @@ class MultiStreamTracker:
             raise NotImplementedError(
                 'camera-motion compensation (cmc) is not supported by MultiStreamTracker: its state would live inside '
                 'the batched GPU association; use OCSORT_Disparity (test_step / test_steps) for a tracker with cmc')
+        if getattr(model, 'stereo_eval', None) is not None:
+            raise NotImplementedError(
+                'stereo_eval (the dense disparity evaluator) is not wired into MultiStreamTracker; use OCSORT_Disparity '
+                '(test_step / test_steps) for a model with stereo_eval set')
         self.max_tracks = int(max_tracks)
         self.max_dets = int(model.max_det if max_dets is None else max_dets)
         if not 1 <= self.max_dets <= int(model.max_det):

@@ -324,6 +324,9 @@ def track_gathered(dets, counts, num_frames, tracker, model):
         # consecutive frames may have been detected on different ranks: no rank holds the image pairs
         raise NotImplementedError('camera-motion compensation (tracker cmc) is not supported by the sharded driver; '
                                   'run the video through OCSORT_Disparity.predict on one device')
+    if getattr(model, 'stereo_eval', None) is not None:
+        raise NotImplementedError('stereo_eval (the dense disparity evaluator) is not wired into the sharded driver; '
+                                  'run the video through OCSORT_Disparity.predict on one device')
     dets = dets.cpu()
     results = []
     for t in range(num_frames):
