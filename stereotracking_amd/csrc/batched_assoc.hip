@@ -1,7 +1,8 @@
 // Batched GPU association: the depth-guided OC-SORT step of MANY independent sequences advanced in
 // lockstep on the device - one workgroup (one wave) per sequence and frame.
 //
-// Behavioural spec = the host routine csrc/ocsort_tracker.cpp (st_tracker_track), i.e. reference
+// Behavioural spec = the host routine csrc/ocsort_tracker.cpp (st_tracker_track), i.e. reference (the Kalman filter, the
+// box helpers, the observation history and the feeding of a track are the host routine's own: csrc/ocsort_core.h)
 //   OCSORTTracker_Disparity.track            mmtrack/models/trackers/ocsort_tracker_disparity.py:345-618
 //     ocm_assign_ids / ocr_assign_ids / online_smooth          :187-265, :273-317, :319-343
 //   KalmanFilter initiate / predict / update                   mmtrack/models/motion/kalman_filter.py:60-189
@@ -32,30 +33,15 @@
 #include <memory>
 #include <vector>
 
+#include "ocsort_core.h"
 #include "st_common.h"
 
 namespace st {
 namespace ba {
 
-constexpr int WINCAP = 8;           // vel_delta_t + 1 <= 8 observations kept per track
+using namespace oc;   // KState, DTrack, WINCAP, the Kalman filter, the box helpers and the routines that feed a track
+
 constexpr double kBig = 1000000.0;
-constexpr double kWPos = 1.0 / 20, kWVel = 1.0 / 160;
-
-struct KState { double mean[8]; double cov[64]; };
-
-struct DTrack {
-  long long id;
-  KState kf, saved;
-  int tentative, tracked, last_frame, n_fed;
-  float win[WINCAP][4];
-  int win_valid[WINCAP];
-  int win_len;
-  long long n_obs;
-  float last_valid[4];
-  int trailing_none;
-  float vel[2];
-  int vel_placeholder;
-};
 
 // `poisoned`: sticky status of the sequence.  A capacity overflow is detected after the association has already
 // mutated the tracks (Kalman predictions, observation windows, ids handed out), so the sequence is INVALID from then
@@ -67,193 +53,6 @@ struct Cfg {
   int weight_iou_with_det_scores, num_tentatives, vel_delta_t, num_frames_retain;
   int max_tracks, max_dets;
 };
-
-// ---- Kalman filter (float64; the loops of ocsort_tracker.cpp) ---------------------------------------------------
-__device__ void kf_initiate(const float meas[4], KState& s) {
-  for (int i = 0; i < 4; ++i) { s.mean[i] = (double)meas[i]; s.mean[4 + i] = 0.0; }
-  const double h = (double)meas[3];
-  const double sd[8] = {2 * kWPos * h, 2 * kWPos * h, 1e-2, 2 * kWPos * h,
-                        10 * kWVel * h, 10 * kWVel * h, 1e-5, 10 * kWVel * h};
-  for (int i = 0; i < 64; ++i) s.cov[i] = 0.0;
-  for (int i = 0; i < 8; ++i) s.cov[i * 8 + i] = sd[i] * sd[i];
-}
-
-__device__ void kf_predict(KState& s) {
-  const double h = s.mean[3];
-  const double sd[8] = {kWPos * h, kWPos * h, 1e-2, kWPos * h, kWVel * h, kWVel * h, 1e-5, kWVel * h};
-  for (int i = 0; i < 4; ++i) s.mean[i] = s.mean[i] + s.mean[i + 4];
-  double t[64];
-  for (int i = 0; i < 8; ++i)
-    for (int j = 0; j < 8; ++j) t[i * 8 + j] = j < 4 ? s.cov[i * 8 + j] + s.cov[i * 8 + j + 4] : s.cov[i * 8 + j];
-  for (int i = 0; i < 8; ++i)
-    for (int j = 0; j < 8; ++j) s.cov[i * 8 + j] = i < 4 ? t[i * 8 + j] + t[(i + 4) * 8 + j] : t[i * 8 + j];
-  for (int i = 0; i < 8; ++i) s.cov[i * 8 + i] += sd[i] * sd[i];
-}
-
-__device__ void kf_update(KState& s, const float meas[4]) {
-  const double h = s.mean[3];
-  const double sd[4] = {kWPos * h, kWPos * h, 1e-1, kWPos * h};
-  double S[16];
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) S[i * 4 + j] = s.cov[i * 8 + j] + (i == j ? sd[i] * sd[i] : 0.0);
-  double L[16];
-  for (int i = 0; i < 16; ++i) L[i] = 0.0;
-  for (int j = 0; j < 4; ++j) {
-    double d = S[j * 4 + j];
-    for (int k = 0; k < j; ++k) d -= L[j * 4 + k] * L[j * 4 + k];
-    d = sqrt(d);
-    L[j * 4 + j] = d;
-    for (int i = j + 1; i < 4; ++i) {
-      double v = S[i * 4 + j];
-      for (int k = 0; k < j; ++k) v -= L[i * 4 + k] * L[j * 4 + k];
-      L[i * 4 + j] = v / d;
-    }
-  }
-  double X[32];
-  for (int c = 0; c < 8; ++c) {
-    double y[4];
-    for (int i = 0; i < 4; ++i) {
-      double v = s.cov[c * 8 + i];
-      for (int k = 0; k < i; ++k) v -= L[i * 4 + k] * y[k];
-      y[i] = v / L[i * 4 + i];
-    }
-    for (int i = 3; i >= 0; --i) {
-      double v = y[i];
-      for (int k = i + 1; k < 4; ++k) v -= L[k * 4 + i] * X[k * 8 + c];
-      X[i * 8 + c] = v / L[i * 4 + i];
-    }
-  }
-  double innov[4];
-  for (int i = 0; i < 4; ++i) innov[i] = (double)meas[i] - s.mean[i];
-  for (int c = 0; c < 8; ++c) {
-    double acc = 0.0;
-    for (int r = 0; r < 4; ++r) acc += innov[r] * X[r * 8 + c];
-    s.mean[c] += acc;
-  }
-  double SX[32];
-  for (int r = 0; r < 4; ++r)
-    for (int c = 0; c < 8; ++c) {
-      double acc = 0.0;
-      for (int k = 0; k < 4; ++k) acc += S[r * 4 + k] * X[k * 8 + c];
-      SX[r * 8 + c] = acc;
-    }
-  for (int i = 0; i < 8; ++i)
-    for (int j = 0; j < 8; ++j) {
-      double acc = 0.0;
-      for (int k = 0; k < 4; ++k) acc += X[k * 8 + i] * SX[k * 8 + j];
-      s.cov[i * 8 + j] -= acc;
-    }
-}
-
-// ---- float32 box helpers (single IEEE ops, reference order) -----------------------------------------------------
-__device__ inline void xyxy_to_cxcyah(const float b[4], float o[4]) {
-  o[0] = (b[2] + b[0]) / 2;
-  o[1] = (b[3] + b[1]) / 2;
-  const float w = b[2] - b[0], h = b[3] - b[1];
-  o[2] = w / h;
-  o[3] = h;
-}
-__device__ inline void cxcyah_to_xyxy(const float b[4], float o[4]) {
-  const float w = b[2] * b[3];
-  o[0] = b[0] - w / 2.0f;
-  o[1] = b[1] - b[3] / 2.0f;
-  o[2] = b[0] + w / 2.0f;
-  o[3] = b[1] + b[3] / 2.0f;
-}
-__device__ inline float tmax(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
-__device__ inline float tmin(float a, float b) { return a != a ? a : (b != b ? b : (a < b ? a : b)); }
-__device__ inline float iou(const float a[4], const float b[4]) {
-  const float area1 = (a[2] - a[0]) * (a[3] - a[1]);
-  const float area2 = (b[2] - b[0]) * (b[3] - b[1]);
-  const float w = tmax(tmin(a[2], b[2]) - tmax(a[0], b[0]), 0.f);
-  const float h = tmax(tmin(a[3], b[3]) - tmax(a[1], b[1]), 0.f);
-  const float overlap = w * h;
-  const float uni = tmax(area1 + area2 - overlap, 1e-6f);
-  return overlap / uni;
-}
-
-// ---- observation history ----------------------------------------------------------------------------------------
-__device__ void push_obs(DTrack& t, const float* box, int vel_delta_t) {
-  const int cap = vel_delta_t + 1;
-  if (t.win_len == cap) {
-    for (int k = 1; k < cap; ++k) {
-      for (int e = 0; e < 4; ++e) t.win[k - 1][e] = t.win[k][e];
-      t.win_valid[k - 1] = t.win_valid[k];
-    }
-    --t.win_len;
-  }
-  for (int e = 0; e < 4; ++e) t.win[t.win_len][e] = box ? box[e] : 0.f;
-  t.win_valid[t.win_len] = box != nullptr;
-  ++t.win_len;
-  ++t.n_obs;
-  if (box) {
-    for (int e = 0; e < 4; ++e) t.last_valid[e] = box[e];
-    t.trailing_none = 0;
-  } else {
-    ++t.trailing_none;
-  }
-}
-__device__ const float* k_step_observation(const DTrack& t, int vel_delta_t) {
-  if (t.n_obs > vel_delta_t && t.win_len == vel_delta_t + 1 && t.win_valid[0]) return t.win[0];
-  return t.last_valid;
-}
-__device__ void set_velocity(DTrack& t, const float* b1, const float* b2) {
-  const float s1 = ((b1[0] + b1[1]) + b1[2]) + b1[3], s2 = ((b2[0] + b2[1]) + b2[2]) + b2[3];
-  if (s1 < 0 || s2 < 0) { t.vel[0] = t.vel[1] = -1.f; t.vel_placeholder = 1; return; }
-  const float cx1 = (b1[0] + b1[2]) / 2.0f, cy1 = (b1[1] + b1[3]) / 2.0f;
-  const float cx2 = (b2[0] + b2[2]) / 2.0f, cy2 = (b2[1] + b2[3]) / 2.0f;
-  const float sy = cy2 - cy1, sx = cx2 - cx1;
-  const float norm = sqrtf(sy * sy + sx * sx) + 1e-6f;
-  t.vel[0] = sy / norm;
-  t.vel[1] = sx / norm;
-  t.vel_placeholder = (t.vel[0] + t.vel[1]) == -2.0f;
-}
-__device__ void init_track(DTrack& t, long long id, const float* row, int frame_id, int vel_delta_t) {
-  t.id = id;
-  t.n_fed = 1;
-  t.last_frame = frame_id;
-  t.tentative = frame_id != 0;
-  t.win_len = 0;
-  t.n_obs = 0;
-  t.trailing_none = 0;
-  for (int e = 0; e < 4; ++e) t.last_valid[e] = 0.f;
-  t.vel[0] = t.vel[1] = -1.f;
-  t.vel_placeholder = 1;
-  float m[4];
-  xyxy_to_cxcyah(row, m);
-  kf_initiate(m, t.kf);
-  // no saved filter yet (the reference's track has no such item until its first predict as a tracked, confirmed
-  // track): zero, as the host tracker's value-initialised Track::saved, so that the two states compare equal
-  for (int i = 0; i < 8; ++i) t.saved.mean[i] = 0.0;
-  for (int i = 0; i < 64; ++i) t.saved.cov[i] = 0.0;
-  push_obs(t, row, vel_delta_t);
-  t.tracked = 1;
-}
-__device__ void update_track(DTrack& t, const float* row, int frame_id, const Cfg& cfg) {
-  ++t.n_fed;
-  t.last_frame = frame_id;
-  if (t.tentative && t.n_fed >= cfg.num_tentatives) t.tentative = 0;
-  float m[4];
-  xyxy_to_cxcyah(row, m);
-  kf_update(t.kf, m);
-  t.tracked = 1;
-  push_obs(t, row, cfg.vel_delta_t);
-  set_velocity(t, k_step_observation(t, cfg.vel_delta_t), row);
-}
-__device__ void online_smooth(DTrack& t, const float* new_box) {
-  float last[4];
-  for (int i = 0; i < 4; ++i) last[i] = t.last_valid[i];
-  const int gap = t.trailing_none;
-  float step[4];
-  for (int i = 0; i < 4; ++i) step[i] = (new_box[i] - last[i]) / (float)(gap + 1);
-  t.kf = t.saved;
-  for (int g = 0; g < gap; ++g) {
-    float vb[4], m[4];
-    for (int i = 0; i < 4; ++i) vb[i] = last[i] + (float)(g + 1) * step[i];
-    xyxy_to_cxcyah(vb, m);
-    kf_update(t.kf, m);
-  }
-}
 
 // ---- dense Jonker-Volgenant on lap's (R + C)^2 extension, never materialised: at(i, j) is computed ----------------
 struct Lap {
@@ -550,7 +349,9 @@ __device__ inline Scratch carve(char* base, int T, int M) {
 }
 
 // one association stage: rows = tracks tidx[0..R), cols = detections pool[0..Cn) -> d2r[c] = row matched to column c
-// or -1.  The cost matrix is filled by all 64 lanes, the assignment runs on lane 0.
+// or -1.  The cost matrix is filled by all 64 lanes, the assignment runs on lane 0.  An entry is cost_entry
+// (ocsort_core.h), as in StTracker::assign (ocsort_tracker.cpp); what a track brings to its row (tb, ko, valid) is
+// written out in both loops: as a shared routine it changes this kernel's code.
 __device__ void assign_stage(const Cfg& cfg, DTrack* tracks, const int* tidx, int R, const int* pool, int Cn,
                              const float* dets, bool with_motion, Scratch& s, int lane) {
   for (int c = lane; c < Cn; c += 64) s.d2r[c] = -1;
@@ -571,20 +372,8 @@ __device__ void assign_stage(const Cfg& cfg, DTrack* tracks, const int* tidx, in
     const float* ko = with_motion ? k_step_observation(t, cfg.vel_delta_t) : nullptr;
     const bool valid = with_motion && !t.vel_placeholder && (((ko[0] + ko[1]) + ko[2]) + ko[3]) != -4.0f;
     const float* dd = dets + (size_t)pool[c] * 8;
-    float v = iou(tb, dd);
-    if (cfg.weight_iou_with_det_scores) v = v * dd[4];
-    float dist = 1.0f - v;
-    if (with_motion) {
-      const float cx1 = (ko[0] + ko[2]) / 2.0f, cy1 = (ko[1] + ko[3]) / 2.0f;
-      const float cx2 = (dd[0] + dd[2]) / 2.0f, cy2 = (dd[1] + dd[3]) / 2.0f;
-      const float sy = cy2 - cy1, sx = cx2 - cx1;
-      const float norm = sqrtf(sy * sy + sx * sx) + 1e-6f;
-      float cosv = (sy / norm) * t.vel[0] + (sx / norm) * t.vel[1];
-      cosv = cosv < -1.f ? -1.f : (cosv > 1.f ? 1.f : cosv);
-      const float ang = (acosf(cosv) - (float)(M_PI / 2.)) / (float)M_PI;
-      const float term = ang * (valid ? 1.0f : 0.0f);
-      dist = dist + term * cfg.vel_consist_weight;
-    }
+    const float dist = cost_entry(tb, dd, with_motion, ko, t.vel, valid, cfg.weight_iou_with_det_scores,
+                                  cfg.vel_consist_weight);
     s.cost[(size_t)r * Cn + c] = (double)dist;
   }
   __syncthreads();
@@ -661,9 +450,7 @@ __device__ __forceinline__ void assoc_frame(const Cfg cfg, Scratch s, SeqHeader*
     } else {
       int nc = 0;
       for (int i = 0; i < n; ++i) {
-        const float* d = dets + (size_t)i * 8;
-        const float area = (d[2] - d[0]) * (d[3] - d[1]);
-        if (d[4] > cfg.obj_score_thr && area > 100.f) s.cand[nc++] = i;
+        if (enters_association(dets + (size_t)i * 8, cfg.obj_score_thr)) s.cand[nc++] = i;
       }
       int ncf = 0, nt = 0;
       for (int k = 0; k < hdr->n_tracks; ++k) {
@@ -766,7 +553,7 @@ __device__ __forceinline__ void assoc_frame(const Cfg cfg, Scratch s, SeqHeader*
     const float* row = dets + (size_t)s.order[i] * 8;
     DTrack& t = tracks[s.tidx[i]];
     if (t.id < 0) init_track(t, s.ids[i], row, frame_id, cfg.vel_delta_t);
-    else update_track(t, row, frame_id, cfg);
+    else update_track(t, row, frame_id, cfg.num_tentatives, cfg.vel_delta_t);
     for (int e = 0; e < 8; ++e) orow[(size_t)i * 8 + e] = row[e];
     oid[i] = s.ids[i];
   }
@@ -776,8 +563,7 @@ __device__ __forceinline__ void assoc_frame(const Cfg cfg, Scratch s, SeqHeader*
     int w = 0;
     const int ntr = sh[0];
     for (int k = 0; k < ntr; ++k) {
-      const DTrack& t = tracks[k];
-      const bool drop = frame_id - t.last_frame >= cfg.num_frames_retain || (t.tentative && t.last_frame != frame_id);
+      const bool drop = is_dropped(&tracks[k], frame_id, cfg.num_frames_retain);
       s.rest[k] = drop ? -1 : w;
       if (!drop) ++w;
     }

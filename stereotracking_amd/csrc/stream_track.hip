@@ -15,11 +15,13 @@
 // kernel arguments: a tick needs no host->device copy.  One workgroup per stream (or slot); rows across the lanes.
 //
 // The unscale is reference mmtrack/models/mot/ocsort_disparity.py:95-97 (trackers/utils.py:58-73 scale_bbox) written as
-// the same single fp32 operations as the host routine (ocsort_tracker.cpp, track_records); this file is built with
-// -ffp-contract=off like the rest of the library, so no multiply-add is contracted and the boxes are equal to the bit.
+// the single fp32 operations of unscale_box (ocsort_core.h), which the host routine (ocsort_tracker.cpp, track_records)
+// calls too; this file is built with -ffp-contract=off like the rest of the library, so no multiply-add is contracted
+// and the boxes are equal to the bit.
 #include <cstdint>
 #include <cstring>
 
+#include "ocsort_core.h"
 #include "st_common.h"
 
 namespace st {
@@ -91,12 +93,7 @@ __global__ __launch_bounds__(kThreads) void unscale_kernel(Route route, int max_
   // operand form the library must not contain (tests/test_cpu_oracle_and_abi.py fences it)
 #pragma clang loop vectorize(disable) interleave(disable)
   for (int i = threadIdx.x; i < n; i += kThreads) {
-    const float* r = src + (size_t)i * 8;
-    const float inv = 1.0f / r[7];
-    const float cx = (r[0] + r[2]) / 2.0f, cy = (r[1] + r[3]) / 2.0f;
-    const float w = (r[2] - r[0]) * inv, h = (r[3] - r[1]) * inv;
-    float* b = dst + (size_t)i * 4;
-    b[0] = cx - w / 2.0f; b[1] = cy - h / 2.0f; b[2] = cx + w / 2.0f; b[3] = cy + h / 2.0f;
+    oc::unscale_box(src + (size_t)i * 8, dst + (size_t)i * 4);
   }
 }
 
