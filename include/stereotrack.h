@@ -254,6 +254,15 @@ typedef struct StDetectorConfig {
                          * only): no disp_stem / disp_stage1 parameters or launches, no branch average; stage2 consumes
                          * the RGB stage-1 features.  The disparity input of the forward calls may then be NULL (the
                          * MOT shell still consumes the disparity for the per-box depth, ocsort_disparity.py:82-83). */
+  int out_fd;           /* 1 = the backbone's `out_fd=True` (csp_darknet_disparity_v1.py:72,203-204): the disparity
+                         * branch's stage-1 features BEFORE the average are an output too (tap "stage1_disp", the `df`
+                         * input of the disparity-completion head, section 23).  disp_stage1 then stores its own tensor
+                         * and the average (o_disp + o_rgb) * 0.5 is one more op of the plan; "stage1_fused" and the
+                         * head output are bit-identical to the out_fd = 0 plan.  0 = the plan as before, launch for
+                         * launch.  Not with rgb_only (ST_ERR_INVALID).  The field sits in what used to be the struct's
+                         * tail padding, so sizeof(StDetectorConfig) did not change: a caller that zero-initialises
+                         * the struct (or passes struct_size = offsetof(StDetectorConfig, out_fd)) gets the old plan;
+                         * other values than 0 / 1 are refused. */
 } StDetectorConfig;
 
 int st_detector_create(const StDetectorConfig* cfg, StDetector** out);
@@ -308,7 +317,7 @@ int st_detector_forward_raw(StDetector* det, const unsigned char* const* img_fra
                             st_stream_t stream, float* head_out_dev);
 /* Per-op timing for bench.py / profiling.  When enabled every op (focus pack, conv, spp) of the
  * following forwards is bracketed by hipEvents on the caller's stream; st_detector_op_times
- * synchronises on them and returns, per op: elapsed ms, kind (0 focus, 1 conv, 2 spp), the kernel
+ * synchronises on them and returns, per op: elapsed ms, kind (0 focus, 1 conv, 2 spp, 3 the out_fd average), the kernel
  * instance that ran it (0..21 implicit-GEMM tiles, 40 fused stem, 41 streaming 1x1, 42 direct 3x3,
  * 43 / 44 Winograd, 45 fused front, 46 resident 1x1, 47 head prediction, 48 / 49 grouped Winograd launch
  * and its riders, 50..55 split-operand instances; names: st_conv_variant_name; -1 otherwise), conv MACs, phase. */
@@ -342,8 +351,8 @@ const char* st_conv_variant_signature(int id); /* template args of the variant's
 int st_detector_get_tuning(const StDetector* det, int* variants, int cap);
 int st_detector_set_tuning(StDetector* det, const int* variants, int n);
 /* Internal NHWC activations inside the workspace (valid after forward); name in
- * {"stage1_rgb","stage1_fused","stage2","stage3","stage4","p3_inner","p3","p4","p5"}.  Pixel p, channel c
- * is ptr[p*ld + c]. */
+ * {"stage1_rgb","stage1_fused","stage2","stage3","stage4","p3_inner","p3","p4","p5"}, and "stage1_disp" in an
+ * out_fd plan (valid until the end of the forward, like "p3").  Pixel p, channel c is ptr[p*ld + c]. */
 int st_detector_tap(const StDetector* det, const char* name, const void* workspace_dev,
                     const float** ptr_dev, int* N, int* C, int* H, int* W, int* ld);
 /* The prediction convolutions of the decoupled head on their own (instance 47 of the plan): per level conv_cls
@@ -1347,6 +1356,74 @@ size_t st_stereo_eval_workspace_bytes(const StStereoEvalArgs* args);
 int st_stereo_eval(const StStereoEvalArgs* args, const float* pred_dev, const float* gt_dev, const int32_t* extent_dev,
                    const float* boxes_dev, const int32_t* box_counts_dev, int64_t* counts_dev, double* sums_dev,
                    int64_t* hist_dev, void* workspace_dev, st_stream_t stream);
+
+/* ----------------------------------------------------------------------
+ * 23. Disparity-completion head (DispHeadV2) on the device, csrc/disp_head.hip.  Replaces the forward of the
+ *     reference's mmtrack/models/dense_head/disp_head_v2.py:129-176 (input_transform=None, out_channels=1; CBAM(64, 4,
+ *     no_spatial=True) :126, :264-300) and the rescale of base_disp_head.py:131-139:
+ *
+ *       x = ELU(BN(conv3x3 in_channels -> C))   dconv1_1        x: the stride-8 neck level (detector tap "p3")
+ *       x = ELU(BN(conv3x3 C -> C))             dconv1_2
+ *       x = nearest x2(x)
+ *       g = df * (1 - sigmoid(mlp(avg(df)) + mlp(max(df))))     df: detector tap "stage1_disp" (64 channels, stride 4);
+ *                                                               avg / max per image and channel over H x W,
+ *                                                               mlp = Linear(64, 16), ReLU, Linear(16, 64)
+ *       x = ELU(BN(conv3x3 C + 64 -> 256))      dconv2_1        on cat(x, g)
+ *       x = ELU(BN(conv3x3 256 -> 256))         dconv2_2
+ *       x = nearest x2(x)
+ *       x = ELU(BN(conv3x3 256 -> 128))         dconv3_1
+ *       y = ReLU(conv1x1 128 -> 1 + bias)       reg             -> pred [N][1][4 p3_height][4 p3_width]
+ *
+ *     ELU alpha 1.  The 3x3 convolutions run on the conv primitive of section 1 (act = 0; the Winograd instance where
+ *     the layer qualifies, else the implicit GEMM at the library's tile choice - a function of the shapes alone).  The
+ *     rest are bandwidth kernels: ELU in place (dconv1_1, dconv2_1); ELU + nearest x2 stored into the concat slice /
+ *     the input of dconv3_1 (no ELU-ed low-resolution copy); the channel gate (sum and max with a fixed reduction
+ *     order and no float atomics, MLP + sigmoid, apply into channels [C, C + 64) of the concat); ELU + reg + bias +
+ *     ReLU in one pass over the RAW dconv3_1 output (its ELU-ed form is never written).  Two runs are bit-equal and an
+ *     image's result does not depend on the batch around it.
+ *     Parameters are named like the reference state_dict below the head: dconv1_1.conv.weight, dconv1_1.bn.weight /
+ *     .bias / .running_mean / .running_var, ... dconv3_1.*, reg.conv.weight [1][128][1][1], reg.conv.bias [1],
+ *     cbam.ChannelGate.mlp.1.weight [16][64], .mlp.1.bias, .mlp.3.weight [64][16], .mlp.3.bias.
+ *     st_disp_head_finalize folds BN in fp64, packs (Winograd form included) and uploads; needs a current device.
+ * ---------------------------------------------------------------------- */
+typedef struct StDispHead StDispHead;
+typedef struct StDispHeadConfig {
+  int struct_size;          /* = sizeof(StDispHeadConfig) */
+  int batch;
+  int p3_height, p3_width;  /* size of the stride-8 map: padded input / 8 */
+  int in_channels;          /* channels of the stride-8 level, a multiple of 4 (128 for YOLOX-s) */
+  int channels;             /* C, a multiple of 32 (at most 1024) */
+  double bn_eps;            /* 1e-3 */
+} StDispHeadConfig;
+int st_disp_head_create(const StDispHeadConfig* cfg, StDispHead** out);
+int st_disp_head_destroy(StDispHead* head);
+int st_disp_head_num_params(const StDispHead* head);
+int st_disp_head_param_info(const StDispHead* head, int idx, char* name, int name_cap, int64_t shape[4], int* ndim);
+int st_disp_head_set_param(StDispHead* head, const char* name, const float* host, int64_t numel);
+int st_disp_head_finalize(StDispHead* head);
+size_t st_disp_head_workspace_bytes(const StDispHead* head);
+/* p3 / df: NHWC views, pixel p, channel c at p3_dev[p * p3_ld + p3_off + c] (c < in_channels) and
+ * df_dev[p * df_ld + df_off + c] (c < 64); strides and offsets multiples of 4, pointers 16-byte aligned.  Nothing
+ * outside the two slices is read.  The prediction is written to the workspace (tap "pred") and, when pred_out_dev is
+ * not NULL, to pred_out_dev [N][1][4 p3_height][4 p3_width] as well. */
+int st_disp_head_forward(StDispHead* head, const float* p3_dev, int p3_ld, int p3_off, const float* df_dev, int df_ld,
+                         int df_off, void* workspace_dev, size_t workspace_bytes, st_stream_t stream, float* pred_out_dev);
+/* Internal activations inside the workspace (valid after forward), NHWC, pixel p channel c at ptr[p * ld + c]:
+ * "dconv1_2" (RAW: conv + BN, before the ELU), "gate_scale" ([N][64], the sigmoid s), "cat" ([N][2h][2w][C + 64]),
+ * "dconv2_2" (raw), "dconv3_1_raw", "pred" ([N][4h][4w][1]). */
+int st_disp_head_tap(const StDispHead* head, const char* name, const void* workspace_dev, const float** ptr_dev, int* N,
+                     int* C, int* H, int* W, int* ld);
+/* The rescale of predict(rescale=True): N maps [h][w] -> [H][W], bilinear with torch's align_corners=False rule (source
+ * index (dst + 0.5) * in / out - 0.5, clamped at 0).  As in the reference the source is the map of the PADDED input,
+ * resized straight to img_shape (base_disp_head.py:131-139 does not crop the padding first). */
+int st_disp_head_resize(const float* pred_dev, int N, int h, int w, float* out_dev, int H, int W, st_stream_t stream);
+/* Per-launch timing (tools/disp_head_bench.py): when enabled, the st_disp_head_num_launches() launches of the following
+ * forwards (the five convolutions and the kernels between them, st_disp_head_launch_name) are bracketed by hipEvents on
+ * the caller's stream; st_disp_head_launch_times synchronises on them and returns the elapsed ms per launch. */
+int st_disp_head_set_timing(StDispHead* head, int enable);
+int st_disp_head_num_launches(void);
+const char* st_disp_head_launch_name(int i);
+int st_disp_head_launch_times(StDispHead* head, int cap, float* ms);
 
 /* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).

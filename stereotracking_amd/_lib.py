@@ -41,8 +41,13 @@ class StDetectorConfig(C.Structure):
         ('struct_size', C.c_int), ('widen_factor', C.c_float), ('deepen_factor', C.c_float),
         ('num_classes', C.c_int), ('batch', C.c_int), ('height', C.c_int), ('width', C.c_int),
         ('bn_eps', C.c_double), ('with_right_branch', C.c_int), ('disp_planes_identical', C.c_int),
-        ('rgb_only', C.c_int),
+        ('rgb_only', C.c_int), ('out_fd', C.c_int),
     ]
+
+
+class StDispHeadConfig(C.Structure):
+    _fields_ = [('struct_size', C.c_int), ('batch', C.c_int), ('p3_height', C.c_int), ('p3_width', C.c_int),
+                ('in_channels', C.c_int), ('channels', C.c_int), ('bn_eps', C.c_double)]
 
 
 class StTrackerConfig(C.Structure):
@@ -361,6 +366,21 @@ _PROTOS = {
     'st_stream_record_bytes': (_sz, [_i, _i, _i]),
     'st_stream_gather': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp, _vp]),
     'st_stream_unscale': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp]),
+    'st_disp_head_create': (_i, [C.POINTER(StDispHeadConfig), C.POINTER(_vp)]),
+    'st_disp_head_destroy': (_i, [_vp]),
+    'st_disp_head_num_params': (_i, [_vp]),
+    'st_disp_head_param_info': (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(C.c_int64), C.POINTER(_i)]),
+    'st_disp_head_set_param': (_i, [_vp, C.c_char_p, _vp, C.c_int64]),
+    'st_disp_head_finalize': (_i, [_vp]),
+    'st_disp_head_workspace_bytes': (_sz, [_vp]),
+    'st_disp_head_forward': (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _sz, _vp, _vp]),
+    'st_disp_head_tap': (_i, [_vp, C.c_char_p, _vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
+                              C.POINTER(_i), C.POINTER(_i)]),
+    'st_disp_head_resize': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    'st_disp_head_set_timing': (_i, [_vp, _i]),
+    'st_disp_head_num_launches': (_i, []),
+    'st_disp_head_launch_name': (C.c_char_p, [_i]),
+    'st_disp_head_launch_times': (_i, [_vp, _i, _vp]),
     'st_stream_record': (_i, [C.POINTER(StStreamTick), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

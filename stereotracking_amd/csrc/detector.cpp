@@ -22,6 +22,7 @@
 //   * stage1.0 (3x3/s2) + stage1.1 main|short + blocks.0.conv1 of both branches -> one launch (front_fused.hip)
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -75,6 +76,8 @@ struct HeadPredArgs {
 };
 bool head_pred_applicable(int feat, int nc);
 int head_pred_launch(HeadPredArgs a, int feat, hipStream_t stream);
+int avg2_launch(const float* a, int a_ld, int a_off, const float* b, int b_ld, int b_off, float* out, int out_ld,
+                int out_off, long long pixels, int C, float scale, hipStream_t stream);   // disp_head.hip
 
 namespace {
 
@@ -139,7 +142,7 @@ struct TRef {  // a channel slice of an NHWC buffer
 };
 
 struct Op {
-  enum Type { FOCUS, CONV, SPP, STEM, PRED } type;
+  enum Type { FOCUS, CONV, SPP, STEM, PRED, AVG } type;
   // FOCUS / STEM: src input index (0 = img/left, 1 = disp, 2 = right), dst tensor, dst batch offset
   // (STEM = fused Focus + stem ConvModule, stem_focus_conv.hip; uses pc and out1)
   int focus_input = 0;
@@ -150,6 +153,7 @@ struct Op {
   int split = 0, stride = 1, pad = 0, act = 1;
   float post_scale = 1.f;
   // SPP uses in (x) and out1 (cat buffer, x lives in its first C channels)
+  // AVG (out_fd plans): out1 = (in + res) * post_scale, the two-branch average as an op of its own (disp_head.hip)
   int phase = 0;
   double macs = 0.0;   // conv MACs of this op
   int variant = -1;    // conv tile variant picked at the last launch
@@ -319,6 +323,16 @@ struct StDetector {
     macs += o.macs;
     ops.push_back(o);
   }
+  // y = (a + b) * scale over one channel slice each: the branch average of an out_fd plan, where disp_stage1 keeps
+  // its own tensor (same operation order as the fused epilogue: (v + res) * post_scale)
+  void op_avg(const TRef& a, const TRef& b, const TRef& out, float scale) {
+    Op o;
+    o.type = Op::AVG;
+    o.in = a; o.res = b; o.out1 = out; o.post_scale = scale;
+    o.phase = cur_phase;
+    o.group = cur_group;
+    ops.push_back(o);
+  }
   // ConvModule helper: allocates the output unless `out` is given
   TRef convmodule(const std::string& p, const TRef& in, int cout, int k, int stride, TRef out = TRef()) {
     const int pc = packed_convmodules({p}, in.C, {cout}, k);
@@ -466,7 +480,13 @@ int StDetector::build() {
     ops.push_back(f);
   }
   TRef y = rgb_only ? s1_left : new_tensor(N, H4, W4, c2);
+  const bool out_fd = cfg.out_fd != 0;
   TRef C3 = catTD1.slice(c3, c3);
+  TRef s1_disp;
+  if (out_fd) {   // a buffer of its own that no later op writes: valid until the end of the forward, like "p3"
+    s1_disp = new_tensor(N, H4, W4, c2);
+    taps["stage1_disp"] = s1_disp;
+  }
   begin_group(sbatch, N);
   {
     if (!rgb_only) {
@@ -474,7 +494,14 @@ int StDetector::build() {
                               : convmodule("backbone.disp_stem.conv", window(packed_disp, sbatch), c1, 3, 1);
       TRef d1c = convmodule("backbone.disp_stage1.0", dstem, c2, 3, 2);
       // y = (o_stem + o_disp_stem) / 2   (csp_darknet_disparity_v1.py:184)
-      csp_layer("backbone.disp_stage1.1", d1c, c2, n1, true, window(y, sbatch), window(s1_left, sbatch), 0.5f);
+      if (out_fd) {
+        // out_fd (csp_darknet_disparity_v1.py:72,203-204): the disparity features before the average are an output
+        // of the backbone, so disp_stage1 stores them (no residual, post_scale 1) and the average is its own op
+        csp_layer("backbone.disp_stage1.1", d1c, c2, n1, true, window(s1_disp, sbatch));
+        op_avg(window(s1_disp, sbatch), window(s1_left, sbatch), window(y, sbatch), 0.5f);
+      } else {
+        csp_layer("backbone.disp_stage1.1", d1c, c2, n1, true, window(y, sbatch), window(s1_left, sbatch), 0.5f);
+      }
     }
     TRef s2c = convmodule("backbone.stage2.0", window(y, sbatch), c3, 3, 2);
     csp_layer("backbone.stage2.1", s2c, c3, n2, true, window(C3, sbatch));
@@ -612,13 +639,20 @@ int StDetector::build() {
 
 extern "C" int st_detector_create(const StDetectorConfig* cfg, StDetector** out) {
   if (!cfg || !out) return set_error(ST_ERR_INVALID, "st_detector_create: null argument");
-  ST_REQUIRE(cfg->struct_size == (int)sizeof(StDetectorConfig), "st_detector_create: struct_size mismatch (%d vs %zu)",
-             cfg->struct_size, sizeof(StDetectorConfig));
+  // out_fd is the last field; a caller that stops in front of it (struct_size = offsetof(out_fd)) gets the plan
+  // without it
+  ST_REQUIRE(cfg->struct_size == (int)sizeof(StDetectorConfig) || cfg->struct_size == (int)offsetof(StDetectorConfig, out_fd),
+             "st_detector_create: struct_size mismatch (%d vs %zu)", cfg->struct_size, sizeof(StDetectorConfig));
   ST_REQUIRE(cfg->batch > 0 && cfg->height > 0 && cfg->width > 0 && cfg->height % 32 == 0 && cfg->width % 32 == 0,
              "st_detector_create: height/width must be positive multiples of 32 (got %dx%d)", cfg->height, cfg->width);
   ST_REQUIRE(cfg->widen_factor > 0 && cfg->deepen_factor > 0, "st_detector_create: bad widen/deepen factor");
   auto det = std::make_unique<StDetector>();
-  det->cfg = *cfg;
+  std::memcpy(&det->cfg, cfg, std::min((size_t)cfg->struct_size, sizeof(StDetectorConfig)));
+  if (cfg->struct_size <= (int)offsetof(StDetectorConfig, out_fd)) det->cfg.out_fd = 0;
+  ST_REQUIRE(det->cfg.out_fd == 0 || det->cfg.out_fd == 1, "st_detector_create: out_fd must be 0 or 1 (got %d)",
+             det->cfg.out_fd);
+  ST_REQUIRE(!(det->cfg.out_fd && det->cfg.rgb_only),
+             "st_detector_create: out_fd needs the disparity branch, which an rgb_only plan does not have");
   if (det->cfg.bn_eps <= 0) det->cfg.bn_eps = 1e-3;
   ST_CHECK(det->build());
   *out = det.release();
@@ -786,6 +820,11 @@ int launch_op(StDetector* det, Op& o, int img0, const float* const inputs[3], fl
         a.nc = pcc.cout;
       }
       return head_pred_launch(a, det->convs[o.pred_pcc[0]].cin, stream);
+    }
+    case Op::AVG: {
+      return avg2_launch(resolve(det, o.in, ws, head, img0), o.in.ld, o.in.off, resolve(det, o.res, ws, head, img0),
+                         o.res.ld, o.res.off, resolve(det, o.out1, ws, head, img0), o.out1.ld, o.out1.off,
+                         (long long)o.in.N * o.in.H * o.in.W, o.in.C, o.post_scale, stream);
     }
     case Op::CONV: {
       const PackedConv& pc = det->convs[o.pc];
@@ -1039,7 +1078,7 @@ extern "C" int st_detector_op_times(StDetector* det, int cap, float* ms, int* ki
       t += dt;
     }
     if (ms) ms[i] = t;
-    if (kind) kind[i] = det->ops[i].type == Op::FOCUS ? 0 : det->ops[i].type == Op::SPP ? 2 : 1;  // STEM, PRED count as conv
+    if (kind) kind[i] = det->ops[i].type == Op::FOCUS ? 0 : det->ops[i].type == Op::SPP ? 2 : det->ops[i].type == Op::AVG ? 3 : 1;  // STEM, PRED count as conv; 3 = the out_fd average
     if (variant) variant[i] = det->ops[i].variant;
     if (macs) macs[i] = det->ops[i].macs;
     if (phase) phase[i] = det->ops[i].phase;
@@ -1222,6 +1261,9 @@ extern "C" int st_detector_op_desc(const StDetector* det, int i, char* buf, int 
     snprintf(buf, (size_t)cap, "stem focus+conv6x6 s2 input=%d N=%d Hi=%d Wi=%d Cin=%d Cout=%d  %s", o.focus_input,
              det->cfg.batch, det->cfg.height, det->cfg.width, det->convs[o.pc].stem_planes, det->convs[o.pc].cout,
              det->convs[o.pc].srcs[0].conv_prefix.c_str());
+  } else if (o.type == Op::AVG) {
+    snprintf(buf, (size_t)cap, "avg2 (a + b) * %g N=%dx%d H=%d W=%d C=%d  backbone.disp_stage1 + backbone.stage1 (out_fd)",
+             o.post_scale, o.in.N, det->groups[o.group].count, o.in.H, o.in.W, o.in.C);
   } else if (o.type == Op::SPP) {
     snprintf(buf, (size_t)cap, "spp_pool N=%d H=%d W=%d C=%d", o.in.N, o.in.H, o.in.W, o.in.C);
   } else if (o.type == Op::PRED) {

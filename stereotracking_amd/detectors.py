@@ -8,6 +8,9 @@ strings and accepting the same config kwargs, with every FLOP delegated to the H
                                         (configs/stereo_tracking/ocsort/yolox_s_mmyolo_mot_airdrone.py:40-42 over
                                         configs/_base_/yolox_s_8x8_mmyolo.py:17-19)
   YOLOXPAFPN / YOLOXHead / YOLOXHeadModule   mmyolo 0.2.0 (configs/_base_/yolox_s_8x8_mmyolo.py:30-69)
+  DispHeadV2                            mmtrack/models/dense_head/disp_head_v2.py:18-176 (+ base_disp_head.py:104-139)
+  YOLOX_DISP_Completion_V2              mmtrack/models/multi_task/yolox_disp_completion_v2.py:14-162
+                                        (+ single_stage.py:13-121)
 
 The nn.Modules below only HOLD parameters (named exactly like the reference state_dict, so
 checkpoints load with load_state_dict) and validate config; they have no CPU forward — calling
@@ -16,7 +19,7 @@ them without a GPU raises.
 import torch
 import torch.nn as nn
 
-from .engine import HipDetector
+from .engine import HipDetector, HipDispHead
 from .registry import MODELS
 from .structures import InstanceData
 
@@ -58,7 +61,6 @@ class YOLOXCSPDarknet_Disparity_V1_MMYOLO(_ParamHolder):
         if tuple(spp_kernal_sizes) != (5, 9, 13): unsupported.append(f'spp_kernal_sizes={spp_kernal_sizes}')
         if tuple(out_indices) != (2, 3, 4): unsupported.append(f'out_indices={out_indices}')
         if input_channels != 3: unsupported.append(f'input_channels={input_channels}')
-        if out_fd: unsupported.append('out_fd=True')
         if norm_cfg.get('type') not in ('BN', 'SyncBN'): unsupported.append(f'norm {norm_cfg}')
         if act_cfg.get('type') != 'SiLU': unsupported.append(f'act {act_cfg}')
         if unsupported:
@@ -66,6 +68,9 @@ class YOLOXCSPDarknet_Disparity_V1_MMYOLO(_ParamHolder):
                                       'unsupported: ' + ', '.join(unsupported))
         self.deepen_factor, self.widen_factor = float(deepen_factor), float(widen_factor)
         self.bn_eps = float(norm_cfg.get('eps', 1e-5))
+        # out_fd (csp_darknet_disparity_v1.py:72,203-204): the disparity branch's stage-1 features are an output too -
+        # the detector plan then keeps them (tap 'stage1_disp') for the disparity-completion head
+        self.out_fd = bool(out_fd)
 
 
 @MODELS.register_module(name=['CSPDarknet'])
@@ -157,6 +162,7 @@ class YOLODetector_Disparity_V1(nn.Module):
             raise ValueError('backbone / neck / head widen+deepen factors must agree')
         self.widen_factor, self.deepen_factor = w, d
         self.rgb_only = isinstance(self.backbone, CSPDarknet)
+        self.out_fd = bool(getattr(self.backbone, 'out_fd', False))
         self.num_classes = self.bbox_head.num_classes
         if not 1 <= self.num_classes <= 1024:
             raise ValueError('num_classes must be in [1, 1024]')
@@ -214,7 +220,7 @@ class YOLODetector_Disparity_V1(nn.Module):
         eng = self._engines.get(key)
         if eng is None:
             eng = HipDetector(N, H, W, self.widen_factor, self.deepen_factor, self.num_classes,
-                              bn_eps=self.backbone.bn_eps, stereo=stereo, rgb_only=self.rgb_only)
+                              bn_eps=self.backbone.bn_eps, stereo=stereo, rgb_only=self.rgb_only, out_fd=self.out_fd)
             eng.multi_label = self.multi_label
             self._engines[key] = eng
         ver = self._weights_version()
@@ -314,3 +320,125 @@ class YOLODetector(YOLODetector_Disparity_V1):
     configs/_base_/yolox_s_8x8_mmyolo.py:19): the single-stage detector whose backbone `mmtrack.CSPDarknet` picks
     `x['img']` out of the MOT shell's input dict (csp_darknet.py:8-13).  Same HIP plan machinery as the two-branch class;
     with the two-branch backbone configured it behaves exactly like `YOLODetector_Disparity_V1`."""
+
+
+@MODELS.register_module(name=['DispHeadV2'])
+class DispHeadV2(_ParamHolder):
+    """The disparity-completion head (reference disp_head_v2.py:18-176): holds the parameters under the reference's
+    state_dict keys (dconv1_1.conv.weight ... reg.conv.bias, cbam.ChannelGate.mlp.{1,3}.*); the forward runs in the HIP
+    library (engine.HipDispHead).  Anything but the configuration the library implements raises, naming the argument."""
+
+    def __init__(self, in_channels, channels, out_channels=1, in_index=-1, input_transform=None, conv_cfg=None,
+                 norm_cfg=None, act_cfg=None, loss_cfg=None, align_corners=False, init_cfg=None):
+        super().__init__()
+        norm_cfg = norm_cfg or dict(type='BN', momentum=0.03, eps=0.001, requires_grad=True)
+        act_cfg = act_cfg or dict(type='ELU')
+        unsupported = []
+        # inputs = (p3, p4, p5, df): forward reads inputs[:-1][in_index] (:132-133); the head's two x2 upsamplings and
+        # the stride-4 concat need the stride-8 level
+        if in_index not in (0, -3): unsupported.append(f'in_index={in_index} (must select the stride-8 level: 0)')
+        if input_transform is not None: unsupported.append(f'input_transform={input_transform}')
+        if not isinstance(channels, int) or channels <= 0 or channels % 32: unsupported.append(f'channels={channels} (a multiple of 32)')
+        if not isinstance(in_channels, int) or in_channels <= 0 or in_channels % 4:
+            unsupported.append(f'in_channels={in_channels} (a multiple of 4)')
+        if out_channels != 1: unsupported.append(f'out_channels={out_channels}')
+        if conv_cfg: unsupported.append(f'conv_cfg={conv_cfg}')
+        if norm_cfg.get('type') not in ('BN', 'SyncBN'): unsupported.append(f'norm_cfg={norm_cfg} (norm must be BN)')
+        if act_cfg.get('type') != 'ELU' or act_cfg.get('alpha', 1.0) != 1.0: unsupported.append(f'act_cfg={act_cfg} (act must be ELU)')
+        if align_corners: unsupported.append('align_corners=True')
+        if unsupported:
+            raise NotImplementedError('HIP DispHeadV2 supports the reference defaults only; unsupported: ' + ', '.join(unsupported))
+        self.in_channels, self.channels, self.in_index = in_channels, channels, in_index
+        self.bn_eps = float(norm_cfg.get('eps', 1e-5))
+        self.align_corners = False
+        self._table = HipDispHead(1, 1, 1, in_channels, channels, self.bn_eps).param_table()
+        bn_prefixes = set()
+        for name, shape in self._table:
+            is_buf = name.endswith('running_mean') or name.endswith('running_var')
+            init = torch.ones(shape) if name.endswith(('bn.weight', 'running_var')) else torch.zeros(shape)
+            _attach(self, name, init, is_buf)
+            if name.endswith('.bn.weight'):
+                bn_prefixes.add(name[:-len('.weight')])
+        for p in sorted(bn_prefixes):
+            _attach(self, p + '.num_batches_tracked', torch.zeros((), dtype=torch.long), True)
+
+
+@MODELS.register_module(name=['YOLOX_DISP_Completion_V2'])
+class YOLOX_DISP_Completion_V2(YOLODetector_Disparity_V1):
+    """YOLOX plus the disparity-completion head (reference multi_task/yolox_disp_completion_v2.py:14-162 over
+    single_stage.py:13-121): the detector plan with out_fd, and DispHeadV2 on its 'p3' and 'stage1_disp' taps.
+    `predict` returns (det_results, results_list_disp).  Checkpoint keys `disp_head.*` belong to the head; the
+    detector's own parameter table is that of YOLODetector_Disparity_V1."""
+
+    def __init__(self, backbone, neck, bbox_head, disparity_head=None, train_cfg=None, test_cfg=None,
+                 data_preprocessor=None, init_cfg=None, use_syncbn=True):
+        super().__init__(backbone, neck, bbox_head, train_cfg=train_cfg, test_cfg=test_cfg,
+                         data_preprocessor=data_preprocessor, init_cfg=init_cfg, use_syncbn=use_syncbn)
+        if disparity_head is None:
+            raise ValueError('YOLOX_DISP_Completion_V2 needs disparity_head=dict(type="DispHeadV2", ...)')
+        if not self.out_fd:
+            raise ValueError('YOLOX_DISP_Completion_V2 needs a backbone with out_fd=True: the head reads the disparity '
+                             "branch's stage-1 features")
+        disparity_head = dict(disparity_head)
+        disparity_head.setdefault('type', 'DispHeadV2')
+        self.disp_head = MODELS.build(disparity_head)
+        if not isinstance(self.disp_head, DispHeadV2):
+            raise NotImplementedError(f'disparity_head type {type(self.disp_head).__name__} (only DispHeadV2)')
+        import math
+        if self.disp_head.in_channels != int(math.ceil(256 * self.widen_factor / 8) * 8):
+            raise ValueError(f'disparity_head.in_channels={self.disp_head.in_channels} does not match the neck '
+                             f'(out_channels {int(math.ceil(256 * self.widen_factor / 8) * 8)})')
+        if int(math.ceil(128 * self.widen_factor / 8) * 8) != 64:
+            raise NotImplementedError('DispHeadV2 gates 64 disparity-feature channels (CBAM(64, 4)): widen_factor must '
+                                      'give a 64-channel stage 1 (0.5)')
+        self._head_engines, self._head_uploaded = {}, {}
+        self._last_engine = None
+
+    def head_config(self):
+        """kwargs of engine.HipDispHead / StereoDensePipeline(disp_head=...) for this model's head."""
+        return dict(in_channels=self.disp_head.in_channels, channels=self.disp_head.channels, bn_eps=self.disp_head.bn_eps)
+
+    def _run(self, batch_inputs, valid_hw=None):
+        eng, head = super()._run(batch_inputs, valid_hw)
+        self._last_engine = eng
+        return eng, head
+
+    def _head_engine(self, eng):
+        key = (eng.batch, eng.height // 8, eng.width // 8)
+        he = self._head_engines.get(key)
+        if he is None:
+            he = self._head_engines[key] = HipDispHead(*key, **self.head_config())
+        ver = tuple(t._version for t in self.disp_head.state_dict(keep_vars=True).values())
+        if self._head_uploaded.get(key) != ver:
+            he.load_state_dict(self.disp_head.state_dict())
+            self._head_uploaded[key] = ver
+        return he
+
+    def _dense_disp(self, eng):
+        """(N,1,H/2,W/2): the head on the taps the detector forward just left in `eng`'s workspace."""
+        return self._head_engine(eng).forward(eng)
+
+    def _forward(self, batch_inputs, batch_data_samples=None):
+        """-> {'forward_bbox': (cls_scores, bbox_preds, objectnesses), 'forward_disp': (N,1,H/2,W/2)} (reference
+        yolox_disp_completion_v2.py:146-162)."""
+        eng, head = self._run(batch_inputs)
+        return dict(forward_bbox=eng.head_nchw(head), forward_disp=self._dense_disp(eng))
+
+    def predict(self, batch_inputs, batch_data_samples, rescale=True):
+        """Reference single_stage.py:68-105: (data samples with pred_instances, results_list_disp).  results_list_disp[i]
+        is (1,h,w) at half the PADDED input's resolution, or with rescale (1,1,*img_shape): bilinear, align_corners=False,
+        straight from the padded map (base_disp_head.py:131-139 does not crop first)."""
+        samples = super().predict(batch_inputs, batch_data_samples, rescale=rescale)
+        eng = self._last_engine
+        he = self._head_engine(eng)
+        pred = he.forward(eng)
+        out = []
+        for i, sm in enumerate(samples):
+            if rescale:
+                shape = sm.metainfo.get('img_shape')
+                if shape is None:
+                    raise KeyError("predict(rescale=True) needs 'img_shape' in every data sample's metainfo")
+                out.append(he.resize(pred[i:i + 1], shape[:2]))
+            else:
+                out.append(pred[i])
+        return samples, out

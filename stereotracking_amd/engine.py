@@ -9,7 +9,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from ._lib import StDecodeDesc, StDetectorConfig, check, current_stream, ptr
+from ._lib import StDecodeDesc, StDetectorConfig, StDispHeadConfig, check, current_stream, ptr
 
 
 def _require_cuda(t, name):
@@ -64,22 +64,28 @@ class HipDetector:
     """
 
     def __init__(self, batch, height, width, widen_factor=0.5, deepen_factor=0.33, num_classes=1,
-                 bn_eps=1e-3, stereo=False, disp_replicated=None, rgb_only=False):
+                 bn_eps=1e-3, stereo=False, disp_replicated=None, rgb_only=False, out_fd=False):
         """disp_replicated: the three planes of disp_postp are identical (a 3-channel repeat of one map), so the
         disparity stem may read plane 0 with plane-summed weights.  Default: True for stereo contexts (the
         disparity then comes from st_disp_upsample_pack, which writes exactly that), False otherwise.
         rgb_only: the single-branch detector of the reference's RGB configuration (backbone `mmtrack.CSPDarknet`,
         csp_darknet.py:8-13): no disparity branch in the plan or the parameter table; `disp` of the forward calls is
-        ignored and may be None."""
+        ignored and may be None.
+        out_fd: the backbone's `out_fd=True` (csp_darknet_disparity_v1.py:72,203-204): the plan also keeps the disparity
+        branch's stage-1 features (tap 'stage1_disp', the `df` input of HipDispHead) and averages the branches in an op
+        of its own; head output and 'stage1_fused' are bit-identical to the plan without it."""
         self.lib = _lib.load()
         self.batch, self.height, self.width = int(batch), int(height), int(width)
         self.stereo = bool(stereo)
         self.rgb_only = bool(rgb_only)
+        self.out_fd = bool(out_fd)
+        if self.out_fd and self.rgb_only:
+            raise ValueError('out_fd needs the disparity branch: rgb_only=True has none')
         self.widen_factor, self.deepen_factor = float(widen_factor), float(deepen_factor)
         self.disp_replicated = self.stereo if disp_replicated is None else bool(disp_replicated)
         cfg = StDetectorConfig(C.sizeof(StDetectorConfig), float(widen_factor), float(deepen_factor),
                                int(num_classes), self.batch, self.height, self.width, float(bn_eps),
-                               int(self.stereo), int(self.disp_replicated), int(self.rgb_only))
+                               int(self.stereo), int(self.disp_replicated), int(self.rgb_only), int(self.out_fd))
         h = C.c_void_p()
         check(self.lib.st_detector_create(C.byref(cfg), C.byref(h)), 'st_detector_create')
         self.handle = h
@@ -321,6 +327,122 @@ class HipDetector:
                 torch.empty(N, max_det, dtype=torch.int64, device=dev),
                 torch.empty(N, max_det, dtype=torch.int32, device=dev),
                 torch.empty(N, dtype=torch.int32, device=dev))
+
+
+class HipDispHead:
+    """DispHeadV2 (reference mmtrack/models/dense_head/disp_head_v2.py:129-176) for a fixed (batch, p3 height, p3 width):
+    the handle of include/stereotrack.h section 23.  `forward(det)` reads the detector context's taps 'p3' and
+    'stage1_disp' (an out_fd plan) where the detector's forward left them, on the current stream."""
+
+    def __init__(self, batch, p3_height, p3_width, in_channels=128, channels=256, bn_eps=1e-3):
+        self.lib = _lib.load()
+        self.batch, self.p3_height, self.p3_width = int(batch), int(p3_height), int(p3_width)
+        self.in_channels, self.channels = int(in_channels), int(channels)
+        cfg = StDispHeadConfig(C.sizeof(StDispHeadConfig), self.batch, self.p3_height, self.p3_width, self.in_channels,
+                               self.channels, float(bn_eps))
+        h = C.c_void_p()
+        check(self.lib.st_disp_head_create(C.byref(cfg), C.byref(h)), 'st_disp_head_create')
+        self.handle = h
+        self.out_hw = (4 * self.p3_height, 4 * self.p3_width)
+        self._ws = None
+
+    def __del__(self):
+        h = getattr(self, 'handle', None)
+        if h:
+            self.lib.st_disp_head_destroy(h)
+            self.handle = None
+
+    def param_table(self):
+        """[(name, shape)] named like the reference state_dict below the head (float tensors only)."""
+        out = []
+        name = C.create_string_buffer(256)
+        shape = (C.c_int64 * 4)()
+        nd = C.c_int()
+        for i in range(self.lib.st_disp_head_num_params(self.handle)):
+            check(self.lib.st_disp_head_param_info(self.handle, i, name, 256, shape, C.byref(nd)))
+            out.append((name.value.decode(), tuple(shape[j] for j in range(nd.value))))
+        return out
+
+    def load_state_dict(self, sd, prefix=''):
+        """Set every parameter (extra keys such as `num_batches_tracked` are ignored), fold BN in fp64, pack, upload."""
+        for name, shape in self.param_table():
+            key = prefix + name
+            if key not in sd:
+                raise KeyError(f'state_dict is missing "{key}"')
+            t = sd[key].detach().to('cpu', torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f'{key}: expected shape {shape}, got {tuple(t.shape)}')
+            check(self.lib.st_disp_head_set_param(self.handle, name.encode(), ptr(t), t.numel()),
+                  f'st_disp_head_set_param({name})')
+        check(self.lib.st_disp_head_finalize(self.handle), 'st_disp_head_finalize')
+
+    def workspace_bytes(self):
+        return int(self.lib.st_disp_head_workspace_bytes(self.handle))
+
+    def _workspace(self, device):
+        if self._ws is None or self._ws.device != device:
+            self._ws = torch.empty(self.workspace_bytes(), dtype=torch.uint8, device=device)
+        return self._ws
+
+    def forward_views(self, p3, df, out=None, workspace=None):
+        """p3 (N,h,w,in_channels) and df (N,2h,2w,64): NHWC views, possibly channel slices of wider buffers (pixel
+        stride = stride(2), contiguous otherwise) -> pred (N,1,4h,4w).  `workspace`: a uint8 tensor of workspace_bytes()
+        to run in (default: the context's own)."""
+        N, h, w = self.batch, self.p3_height, self.p3_width
+        for t, nm, shp in ((p3, 'p3', (N, h, w, self.in_channels)), (df, 'df', (N, 2 * h, 2 * w, 64))):
+            if not (t.is_cuda and t.dtype == torch.float32) or tuple(t.shape) != shp:
+                raise ValueError(f'{nm}: expected a float32 CUDA view of shape {shp}, got {tuple(t.shape)}')
+            ld = t.stride(2)
+            if t.stride(3) != 1 or t.stride(1) != shp[2] * ld or t.stride(0) != shp[1] * shp[2] * ld:
+                raise ValueError(f'{nm}: not a channel slice of a dense NHWC buffer (strides {t.stride()})')
+        ws = workspace if workspace is not None else self._workspace(p3.device)
+        if out is None:
+            out = torch.empty(N, 1, 4 * h, 4 * w, dtype=torch.float32, device=p3.device)
+        check(self.lib.st_disp_head_forward(self.handle, C.c_void_p(p3.data_ptr()), p3.stride(2), 0,
+                                            C.c_void_p(df.data_ptr()), df.stride(2), 0, ptr(ws), ws.numel(),
+                                            current_stream(), ptr(out)), 'st_disp_head_forward')
+        self._last_ws = ws
+        return out
+
+    def forward(self, det, out=None):
+        """The head on a HipDetector context whose forward has just run (out_fd plan): reads its 'p3' and 'stage1_disp'
+        taps in place.  Enqueue it before that context's workspace is reused."""
+        if not getattr(det, 'out_fd', False):
+            raise RuntimeError('HipDispHead.forward needs a detector plan built with out_fd=True (tap "stage1_disp")')
+        return self.forward_views(det.tap('p3'), det.tap('stage1_disp'), out)
+
+    def tap(self, name):
+        """Internal NHWC activation (N,H,W,C) of the last forward, a view into its workspace."""
+        p = C.c_void_p()
+        n, c, h, w, ld = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        ws = self._last_ws
+        check(self.lib.st_disp_head_tap(self.handle, name.encode(), ptr(ws), C.byref(p), C.byref(n), C.byref(c),
+                                        C.byref(h), C.byref(w), C.byref(ld)), 'st_disp_head_tap')
+        flat = ws.view(torch.float32)
+        off = flat.storage_offset() + (p.value - ws.data_ptr()) // 4     # as_strided counts from the storage's start
+        return flat.as_strided((n.value, h.value, w.value, c.value),
+                               (h.value * w.value * ld.value, w.value * ld.value, ld.value, 1), off)
+
+    def set_timing(self, enable=True):
+        check(self.lib.st_disp_head_set_timing(self.handle, int(bool(enable))), 'st_disp_head_set_timing')
+
+    def launch_times(self):
+        """[(launch name, ms)] of the last forward run under set_timing(True); synchronises on its events."""
+        n = self.lib.st_disp_head_num_launches()
+        ms = (C.c_float * n)()
+        check(self.lib.st_disp_head_launch_times(self.handle, n, ms), 'st_disp_head_launch_times')
+        return [(self.lib.st_disp_head_launch_name(i).decode(), float(ms[i])) for i in range(n)]
+
+    def resize(self, pred, size, out=None):
+        """predict(rescale=True) of the reference (base_disp_head.py:131-139): (N,1,h,w) -> (N,1,H,W), bilinear,
+        align_corners=False, from the map of the PADDED input straight to `size` (= img_shape)."""
+        _require_cuda(pred, 'pred')
+        N, h, w = pred.shape[0], pred.shape[-2], pred.shape[-1]
+        H, W = int(size[0]), int(size[1])
+        if out is None:
+            out = torch.empty(N, 1, H, W, dtype=torch.float32, device=pred.device)
+        check(self.lib.st_disp_head_resize(ptr(pred), N, h, w, ptr(out), H, W, current_stream()), 'st_disp_head_resize')
+        return out
 
 
 def state_dict_from_table(table, tensors):

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib, records
 from ._lib import check, current_stream, ptr
-from .engine import HipDetector, RawChunk, _require_cuda
+from .engine import HipDetector, HipDispHead, RawChunk, _require_cuda
 from .stereo import StereoCostVolume
 
 
@@ -118,7 +118,7 @@ class StereoDensePipeline:
                  stereo=True, max_disp=192, feat_stride=4, temperature=32.0, score_thr=0.01, iou_thr=0.5,
                  max_det=1000, baseline=0.25, focal_length=640, pad_size_divisor=32, agg_layers=0, agg3d_layers=0,
                  split_bf16=None, multi_label=True, rgb_only=False, full_res=False, full_res_channels=8, sgbm=None,
-                 depth_method='reference', lr_check=False, lr_max_diff=1.0):
+                 depth_method='reference', lr_check=False, lr_max_diff=1.0, disp_head=None):
         """max_det: rows of the fixed-size detection buffer per frame.  The reference applies NO cap on the
         kept boxes (yolox_style=True => max_per_img = len(results)), so this is a
         capacity, not a threshold: `run()` reports `overflow` whenever a frame kept more boxes than fit, and
@@ -133,7 +133,13 @@ class StereoDensePipeline:
         extract_depth, launched through st_box_depth exactly as before).
 
         lr_check / lr_max_diff: the stereo module's left-right check (stereo.py): pixels that fail it are 0 in disp_postp -
-        so they drop out of the per-box depth - and `run()` also returns `disp_mask` (N,1,H,W), 1 = valid."""
+        so they drop out of the per-box depth - and `run()` also returns `disp_mask` (N,1,H,W), 1 = valid.
+
+        disp_head: dict(in_channels=, channels=, bn_eps=) - the disparity-completion head (DispHeadV2, engine.HipDispHead).
+        The detector plan is then built with out_fd; the head runs on the context's stream right after the detector
+        forward, on the 'p3' and 'stage1_disp' taps in the context's workspace (so before that workspace is reused), and
+        `run()` also returns `dense_disp` (N,1,H/2,W/2), the completed disparity of the PADDED input at half resolution.
+        Parameters: `disp_head.*`.  None: nothing changes."""
         self.depth_method = str(depth_method)
         self._depth_code = depth_method_code(depth_method)
         self.lib = _lib.load()
@@ -184,14 +190,19 @@ class StereoDensePipeline:
         # mmtrack.CSPDarknet); the disparity (loaded, or from the stereo module) is then consumed by box_depth only
         self.rgb_only = bool(rgb_only)
         self.det = HipDetector(self.batch, self.height, self.width, widen_factor, deepen_factor, num_classes,
-                               stereo=self.stereo, rgb_only=self.rgb_only)
+                               stereo=self.stereo, rgb_only=self.rgb_only, out_fd=disp_head is not None)
+        self.disp_head = None
+        if disp_head is not None:
+            cfg = {k: v for k, v in dict(disp_head).items() if k != 'type'}
+            self.disp_head = HipDispHead(self.batch, self.height // 8, self.width // 8, **cfg)
         self.det.multi_label = bool(multi_label)     # several classes: test_cfg.multi_label
         self._bufs = None
 
     # ---- parameters ------------------------------------------------------------------------------
     def param_table(self):
         """Detector parameters (reference state_dict names) + `stereo.agg.*` of the stereo module."""
-        return self.det.param_table() + [('stereo.' + n, shp) for n, shp in self.stereo_module.param_table()]
+        return (self.det.param_table() + [('stereo.' + n, shp) for n, shp in self.stereo_module.param_table()] +
+                ([('disp_head.' + n, shp) for n, shp in self.disp_head.param_table()] if self.disp_head is not None else []))
 
     def load_state_dict(self, sd, prefix='', autotune=True, tuning_cache=None):
         """Upload weights; then pick conv tile variants by measurement, or restore them from
@@ -202,11 +213,14 @@ class StereoDensePipeline:
         self.det.load_state_dict(sd, prefix)
         pre = prefix + 'stereo.'
         self.stereo_module.load_state_dict({k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)})
+        if self.disp_head is not None:
+            self.disp_head.load_state_dict(sd, prefix + 'disp_head.')
         if not autotune:
             return
         import os
         key = (f'v{self.det.lib.st_version()}_b{self.batch}_{self.height}x{self.width}_w{self.det.widen_factor:g}'
-               f'_d{self.det.deepen_factor:g}_s{int(self.stereo)}{"r" if self.rgb_only else ""}_a{self.agg_layers}'
+               f'_d{self.det.deepen_factor:g}_s{int(self.stereo)}{"r" if self.rgb_only else ""}'
+               f'{"f" if self.det.out_fd else ""}_a{self.agg_layers}'
                f'_D{self.max_disp // self.feat_stride if self.full_res else self.D}'
                f'{"_F%d" % self.stereo_module.reduce.out_channels if self.full_res else ""}'
                f'_ops{self.det.lib.st_detector_num_ops(self.det.handle)}_{_device_tag()}'
@@ -274,6 +288,8 @@ class StereoDensePipeline:
             b['scaled_boxes'] = torch.empty(N, M, 4, **f32)
             b['decode'] = self.det.decode_buffers(M, dev)   # persistent: st_decode_nms defines every row itself
             b['overflow'] = torch.empty(N, dtype=torch.bool, device=dev)
+            if self.disp_head is not None:
+                b['dense_disp'] = torch.empty(N, 1, H // 2, W // 2, **f32)
             self._bufs = b
         return self._bufs
 
@@ -333,6 +349,8 @@ class StereoDensePipeline:
             if disp_postp is None:
                 raise ValueError('mono pipeline needs disp_postp')
             self.det.forward(img, disp_postp, b['head'])
+        if self.disp_head is not None:     # reads the taps this forward left in the context's workspace
+            self.disp_head.forward(self.det, out=b['dense_disp'])
         boxes, scores, labels, prior, counts = self.det.decode_nms(
             b['head'], self.score_thr, self.iou_thr, self.max_det, (self.ori_h, self.ori_w), out=b['decode'])
         depth, scales, sboxes = self.box_depth(disp_postp, boxes, counts)
@@ -342,6 +360,8 @@ class StereoDensePipeline:
                    disp_postp=disp_postp, head=b['head'])
         if self.lr_check:
             out['disp_mask'] = b['disp_mask']
+        if self.disp_head is not None:
+            out['dense_disp'] = b['dense_disp']
         return out
 
     @staticmethod
@@ -387,7 +407,7 @@ class InflightPipelines:
 
     def __getattr__(self, name):   # geometry / thresholds of the (identical) contexts: batch, max_det, stereo, ...
         if name in ('batch', 'max_det', 'stereo', 'height', 'width', 'ori_h', 'ori_w', 'agg_layers', 'agg3d_layers', 'split_bf16',
-                    'rgb_only', 'full_res', 'sgbm', 'takes_right', 'depth_method', 'lr_check', 'lr_max_diff'):
+                    'rgb_only', 'full_res', 'sgbm', 'takes_right', 'depth_method', 'lr_check', 'lr_max_diff', 'disp_head'):
             return getattr(self.pipes[0], name)
         raise AttributeError(name)
 
