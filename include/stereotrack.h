@@ -1424,6 +1424,21 @@ int st_disp_head_set_timing(StDispHead* head, int enable);
 int st_disp_head_num_launches(void);
 const char* st_disp_head_launch_name(int i);
 int st_disp_head_launch_times(StDispHead* head, int cap, float* ms);
+/* The map the per-box depth stage reads when it takes its depths from the head (pipeline depth_source): ONE launch, at
+ * the PADDED input size, aligned with disp_postp pixel for pixel (image in the top-left corner) - not the squeezed
+ * predict(rescale=True) map above.
+ *   up2  = dense [N][1][H/2][W/2] (the head's prediction) resized to [H][W] by exactly the arithmetic of
+ *          st_disp_head_resize (same operation order, contraction off): mode 1 is bit-equal to that call;
+ *   mode 1 (completed): out = up2;
+ *   mode 2 (fused):     out = disp > 0 ? disp : up2 per pixel, disp = plane 0 of frame n at disp_dev + n *
+ *          disp_frame_stride.  `disp > 0` is false for 0, -0.0, negatives and NaN (the head's value is taken), +Inf is
+ *          kept.  Planes 1.. of disp are never read; in mode 1 disp is not read at all.
+ *   filled_dev [N] (may be NULL): pixels of frame n inside [0, ext_h) x [0, ext_w) whose value came from the head (all of
+ *          them in mode 1).  Zeroed on the stream by this call, then integer atomics: independent of the order.
+ * Refused (non-zero, nothing written or enqueued): null dense / disp / out, N <= 0, H or W odd or not positive, ext_h
+ * outside [1, H], ext_w outside [1, W], mode not 1 or 2, disp_frame_stride < H * W, H * W >= 2^31. */
+int st_disp_fuse(const float* dense_dev, const float* disp_dev, size_t disp_frame_stride, int N, int H, int W, int ext_h,
+                 int ext_w, int mode, float* out_dev, int32_t* filled_dev, st_stream_t stream);
 
 /* ----------------------------------------------------------------------
  * Dataset reader helper (host, no GPU): reverse the PNG scanline filters (RFC 2083 6: None/Sub/Up/Average/Paeth).

@@ -377,6 +377,7 @@ _PROTOS = {
     'st_disp_head_tap': (_i, [_vp, C.c_char_p, _vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                               C.POINTER(_i), C.POINTER(_i)]),
     'st_disp_head_resize': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    'st_disp_fuse': (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'st_disp_head_set_timing': (_i, [_vp, _i]),
     'st_disp_head_num_launches': (_i, []),
     'st_disp_head_launch_name': (C.c_char_p, [_i]),

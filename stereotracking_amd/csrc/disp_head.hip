@@ -241,6 +241,104 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__
   }
 }
 
+// The map the per-box depth stage reads (st_disp_fuse): up2 = the head's half-resolution prediction at [H][W] by the
+// arithmetic of bilinear_kernel, expression for expression (mode 1 is bit-equal to it), or - mode 2 - the input disparity
+// wherever that is valid (> 0).  A thread owns 4 output columns of one row: one 16-byte load of disp and one 16-byte
+// store where the quad is whole and 16-byte aligned, scalar accesses otherwise (unaligned rows, the tail of a width that
+// is no multiple of 4).  With the source at exactly half the size (sx = sy = 0.5) its 4 pixels interpolate between the
+// source columns a - 1 .. a + 2 (a = X0 / 2), clamped to the map: 4 loads per source row, not 8.  blockIdx.y = frame.
+// The count of head-filled pixels: a shuffle reduction per wave, the 16 waves of the workgroup through 64 bytes of LDS,
+// then ONE integer atomic per workgroup.  The N counters share a cache line and atomics on one line are served one
+// after the other, about 10 ns each on an MI355X: with one atomic per WAVE (8192 at 8 x 736 x 1280) the counter alone
+// cost 85 us next to a 24 us kernel, which is why the workgroup is as large as it can be - 512 atomics.
+constexpr int FUSE_THREADS = 1024;
+__global__ __launch_bounds__(FUSE_THREADS) void disp_fuse_kernel(const float* __restrict__ dense,
+                                                                 const float* __restrict__ disp, size_t disp_stride, int H,
+                                                                 int W, int ext_h, int ext_w, int mode, float sy, float sx,
+                                                                 float* __restrict__ out, int* __restrict__ filled) {
+  const int n = blockIdx.y, h = H >> 1, w = W >> 1, W4 = (W + 3) >> 2;
+  const int items = H * W4;
+  const float* q = dense + (size_t)n * h * w;
+  const float* dn = disp + (size_t)n * disp_stride;
+  float* on = out + (size_t)n * H * W;
+  int count = 0;
+  ST_SCALAR_LOOP
+  for (int i = blockIdx.x * FUSE_THREADS + threadIdx.x; i < items; i += gridDim.x * FUSE_THREADS) {
+    const int Y = i / W4, X0 = (i - Y * W4) * 4;
+    const float fy = fmaxf(sy * ((float)Y + 0.5f) - 0.5f, 0.f);
+    const int y0 = min((int)fy, h - 1);
+    const int y1 = y0 + (y0 < h - 1 ? 1 : 0);
+    const float ly = fminf(fmaxf(fy - (float)y0, 0.f), 1.f);
+    const float* r0 = q + (size_t)y0 * w;
+    const float* r1 = q + (size_t)y1 * w;
+    // the 8 source values, loaded unconditionally and independently of each other (one wait for all of them); every
+    // x0 / x1 below is one of these four clamped columns, picked by index with selects - the same cell, so the same bits
+    const int a = X0 >> 1;
+    const int c0 = max(a - 1, 0), c1 = min(a, w - 1), c2 = min(a + 1, w - 1), c3 = min(a + 2, w - 1);
+    const float t_0 = r0[c0], t_1 = r0[c1], t_2 = r0[c2], t_3 = r0[c3];
+    const float b_0 = r1[c0], b_1 = r1[c1], b_2 = r1[c2], b_3 = r1[c3];
+    float up[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                // (columns past W - the tail quad - clamp like any other; never stored)
+      const float fx = fmaxf(sx * ((float)(X0 + j) + 0.5f) - 0.5f, 0.f);
+      const int x0 = min((int)fx, w - 1);
+      const int x1 = x0 + (x0 < w - 1 ? 1 : 0);
+      const float lx = fminf(fmaxf(fx - (float)x0, 0.f), 1.f);
+      const float t0 = x0 == c0 ? t_0 : x0 == c1 ? t_1 : x0 == c2 ? t_2 : t_3;
+      const float b0 = x0 == c0 ? b_0 : x0 == c1 ? b_1 : x0 == c2 ? b_2 : b_3;
+      const float t1 = x1 == c0 ? t_0 : x1 == c1 ? t_1 : x1 == c2 ? t_2 : t_3;
+      const float b1 = x1 == c0 ? b_0 : x1 == c1 ? b_1 : x1 == c2 ? b_2 : b_3;
+      const float top = (1.f - lx) * t0 + lx * t1;
+      const float bot = (1.f - lx) * b0 + lx * b1;
+      up[j] = (1.f - ly) * top + ly * bot;
+    }
+    const size_t o = (size_t)Y * W + X0;
+    const bool whole = X0 + 4 <= W;
+    float v[4] = {up[0], up[1], up[2], up[3]};
+    bool head[4] = {true, true, true, true};
+    if (mode == 2) {
+      float d[4] = {0.f, 0.f, 0.f, 0.f};
+      if (whole && ((reinterpret_cast<uintptr_t>(dn + o) & 15) == 0)) {
+        const float4 dv = *reinterpret_cast<const float4*>(dn + o);
+        d[0] = dv.x; d[1] = dv.y; d[2] = dv.z; d[3] = dv.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (X0 + j < W) d[j] = dn[o + j];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        head[j] = !(d[j] > 0.f);                 // 0, -0.0, negatives and NaN take the head's value; +Inf is kept
+        v[j] = head[j] ? up[j] : d[j];
+      }
+    }
+    if (Y < ext_h) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) count += (head[j] && X0 + j < ext_w) ? 1 : 0;
+    }
+    if (whole && ((reinterpret_cast<uintptr_t>(on + o) & 15) == 0)) {
+      *reinterpret_cast<float4*>(on + o) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (X0 + j < W) on[o + j] = v[j];
+    }
+  }
+  if (filled) {                                  // (uniform) every thread arrives here: full waves, a full barrier
+    __shared__ int part[FUSE_THREADS / 64];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) count += __shfl_xor(count, d);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int total = 0;
+#pragma unroll
+      for (int k = 0; k < FUSE_THREADS / 64; ++k) total += part[k];
+      if (total) atomicAdd(filled + n, total);
+    }
+  }
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -587,6 +685,30 @@ extern "C" int st_disp_head_resize(const float* pred_dev, int N, int h, int w, f
   ST_REQUIRE((long long)h * w < (1ll << 31) && (long long)H * W < (1ll << 31), "st_disp_head_resize: map too large");
   hipLaunchKernelGGL(bilinear_kernel, dim3(grid_for((long long)N * H * W)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      pred_dev, N, h, w, out_dev, H, W, (float)h / (float)H, (float)w / (float)W);
+  ST_CHECK_HIP(hipGetLastError());
+  return ST_OK;
+}
+
+extern "C" int st_disp_fuse(const float* dense_dev, const float* disp_dev, size_t disp_frame_stride, int N, int H, int W,
+                            int ext_h, int ext_w, int mode, float* out_dev, int32_t* filled_dev, st_stream_t stream_) {
+  ST_REQUIRE(dense_dev && disp_dev && out_dev, "st_disp_fuse: null pointer");
+  ST_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0, "st_disp_fuse: sizes must be positive (at most 65535 frames)");
+  ST_REQUIRE((H & 1) == 0 && (W & 1) == 0, "st_disp_fuse: H and W must be even (the head predicts at H/2 x W/2), got %d x %d", H, W);
+  ST_REQUIRE((long long)H * W < (1ll << 31), "st_disp_fuse: map too large");
+  ST_REQUIRE(ext_h >= 1 && ext_h <= H && ext_w >= 1 && ext_w <= W, "st_disp_fuse: extent %d x %d outside the %d x %d map",
+             ext_h, ext_w, H, W);
+  ST_REQUIRE(mode == 1 || mode == 2, "st_disp_fuse: mode must be 1 (completed) or 2 (fused), got %d", mode);
+  ST_REQUIRE(disp_frame_stride >= (size_t)H * W, "st_disp_fuse: disp_frame_stride %zu < H * W = %zu", disp_frame_stride,
+             (size_t)H * W);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (filled_dev) ST_CHECK_HIP(hipMemsetAsync(filled_dev, 0, sizeof(int32_t) * (size_t)N, stream));
+  const int h = H / 2, w = W / 2;
+  const long long items = (long long)H * ((W + 3) / 4);
+  // 512 workgroups (8192 waves, two workgroups per CU) at most; the grid-stride loop takes the rest
+  const unsigned gx = (unsigned)std::min<long long>((items + FUSE_THREADS - 1) / FUSE_THREADS, std::max(1, 512 / N));
+  hipLaunchKernelGGL(disp_fuse_kernel, dim3(gx, (unsigned)N), dim3(FUSE_THREADS), 0, stream, dense_dev, disp_dev,
+                     disp_frame_stride, H, W, ext_h, ext_w, mode, (float)h / (float)H, (float)w / (float)W, out_dev,
+                     filled_dev);
   ST_CHECK_HIP(hipGetLastError());
   return ST_OK;
 }

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from . import _lib
 from ._lib import check, current_stream, ptr
 from . import records, shell_inputs
-from .pipeline import InflightPipelines, depth_method_code, launch_box_depth
+from .pipeline import InflightPipelines, depth_method_code, depth_source_code, launch_box_depth
 from .registry import MODELS, TASK_UTILS
 from .shell_inputs import RawFrames
 from .structures import InstanceData, TrackDataSample
@@ -262,15 +262,28 @@ class OCSORT_Disparity(nn.Module):
     `stereo_stats`, a one-frame stereo_eval.StereoStats) and `rectify` (a StereoRectify config for RAW,
     unrectified stereo pairs: each chunk's uint8 left / right frames are undistorted + rectified on the device in one
     launch before the stem and the stereo module read them; results are then in rectified-left coordinates, see
-    StereoRectify.to_raw_boxes; baseline='calibration' / focal_length='calibration' take the rectifier's values)."""
+    StereoRectify.to_raw_boxes; baseline='calibration' / focal_length='calibration' take the rectifier's values).
+    stereo_eval may also carry map='input' | 'depth': which map is scored, disp_postp (default) or the `disp_depth` of a
+    `depth_source` other than 'input' (an option of the completion shell below)."""
+
+    _has_disp_head = False      # OCSORT_Disp_Completion_V2: the pipeline runs DispHeadV2, depth_source may name its map
 
     def __init__(self, detector=None, tracker=None, motion=None, data_preprocessor=None, init_cfg=None,
                  baseline=0.25, focal_length=640, stereo=None, dense_batch=8, inflight=3, max_det=1000,
                  results_device='cpu', autotune=True, tuning_cache=None, results_csv=None, split_bf16=None,
-                 queue_depth=1, depth_extraction='reference', rectify=None, stereo_eval=None):
+                 queue_depth=1, depth_extraction='reference', rectify=None, stereo_eval=None, depth_source='input'):
         super().__init__()
         depth_method_code(depth_extraction)     # ValueError for an unknown estimator, before anything is built
+        # depth_source: the map the per-box depths (detections, their scales, the tracks' `depth` column) are read from.
+        # 'input' = disp_postp; 'completed' / 'fused' need the completion head (OCSORT_Disp_Completion_V2, DESIGN.md 24)
+        if depth_source_code(depth_source) and not self._has_disp_head:
+            raise ValueError(f'depth_source={depth_source!r} reads the disparity-completion head: it is an option of '
+                             f'OCSORT_Disp_Completion_V2, {type(self).__name__} has no such head')
+        self.depth_source = depth_source
         self.stereo_eval = self._stereo_eval_options(stereo_eval)      # None: the dense evaluator is off
+        self.stereo_eval_map = stereo_eval.get('map', 'input') if self.stereo_eval is not None else 'input'
+        if self.stereo_eval_map == 'depth' and depth_source == 'input':
+            raise ValueError("stereo_eval: map='depth' scores disp_depth, the map of a depth_source other than 'input'")
         self.depth_extraction = depth_extraction
         self.data_preprocessor = MODELS.build(data_preprocessor) if data_preprocessor is not None else None
         self.detector = MODELS.build(detector) if detector is not None else None
@@ -347,11 +360,13 @@ class OCSORT_Disparity(nn.Module):
             return None
         if not isinstance(cfg, dict):
             raise TypeError(f'stereo_eval must be None or a dict, got {type(cfg).__name__}')
-        unknown = set(cfg) - {'depth_edges', 'bad_thresholds', 'boxes'}
+        unknown = set(cfg) - {'depth_edges', 'bad_thresholds', 'boxes', 'map'}
         if unknown:
-            raise ValueError(f'stereo_eval: unknown keys {sorted(unknown)} (depth_edges, bad_thresholds, boxes)')
+            raise ValueError(f'stereo_eval: unknown keys {sorted(unknown)} (depth_edges, bad_thresholds, boxes, map)')
         if cfg.get('boxes') not in ('gt', None):
             raise ValueError(f"stereo_eval: boxes must be 'gt' or None, got {cfg.get('boxes')!r}")
+        if cfg.get('map', 'input') not in ('input', 'depth'):
+            raise ValueError(f"stereo_eval: map must be 'input' or 'depth', got {cfg.get('map')!r}")
         edges, taus = _stereo_eval.check_options(cfg.get('depth_edges'), cfg.get('bad_thresholds'))
         return dict(depth_edges=edges, bad_thresholds=taus, boxes=cfg.get('boxes'))
 
@@ -359,7 +374,7 @@ class OCSORT_Disparity(nn.Module):
         """Under the side stream, beside the track-box depth launch: ONE st_stereo_eval call of the chunk's disparity
         against its depth maps; the accumulators start their way to a page-locked buffer that finalize() reads."""
         opt, samples, dev = self.stereo_eval, st['data_samples'], st['dev']
-        disp = job['disp']
+        disp = job['eval_disp']      # disp_postp, or (map='depth') the chunk's disp_depth: same slot, same guard
         H, W = int(disp.shape[-2]), int(disp.shape[-1])
         idx = list(range(s, e)) + [e - 1] * (B - (e - s))      # the padding frames repeat the last one (dropped later)
         ext = []
@@ -464,6 +479,16 @@ class OCSORT_Disparity(nn.Module):
         """Under the context's stream, after chunk `ci` (frames [s, e) of call `st`) has been enqueued on `pipe`: a
         subclass's own per-chunk device work (none here)."""
 
+    @staticmethod
+    def _chunk_img_shape(st, s, e):
+        """The img_shape (h, w) the frames [s, e) of call `st` share: as the reference's predict requires it; a sample
+        without one is taken at its un-padded frame size."""
+        metas = [st['data_samples'][n].metainfo for n in range(s, e)]
+        shapes = {tuple(int(v) for v in (m.get('img_shape') or m['pad_shape'])[:2]) for m in metas}
+        if len(shapes) != 1:
+            raise NotImplementedError('dense_depth_map / depth_source over a chunk needs one img_shape')
+        return shapes.pop()
+
     def _side_stream(self, dev):
         st = self._staging.get(('side_stream', dev))
         if st is None:
@@ -562,6 +587,11 @@ class OCSORT_Disparity(nn.Module):
         s, e = st['chunks'][ci]
         a, b = shell_inputs.chunk_inputs(self, st['img'], st['second'], stereo, s, e, B, runner)
         holder = {}
+        from_head = self.depth_source != 'input'
+        ext = None
+        if from_head:      # where disp_filled counts: the frames' img_shape inside the padded input
+            h, w = self._chunk_img_shape(st, s, e)
+            ext = (min(h, runner.height), min(w, runner.width))
         # staging buffers of a context alternate: it is resubmitted before the chunk it just finished is consumed
         turns = self._staging.setdefault(('ctx_turns', id(runner)), [0] * len(runner))
 
@@ -575,10 +605,18 @@ class OCSORT_Disparity(nn.Module):
             # the depth of the TRACK boxes is read from this chunk's disparity after the association, when the context
             # already runs its next chunk: the stereo module's output cycles through queue_depth + 1 buffers (disp_slot;
             # the read is ordered before the buffer's next rewrite by pipe.disp_guard), the mono input `b` is a
-            # tensor of this chunk's own - no private copy either way
-            holder.update(ctx=ctx, disp=out['disp_postp'], disp_slot=runner.pipes[ctx].disp_slot if stereo else None, host=host, slot=slot)
+            # tensor of this chunk's own - no private copy either way.  With a depth_source other than 'input' the map
+            # read there is the chunk's disp_depth, which lives in a slot of that ring in BOTH configurations
+            holder.update(ctx=ctx, disp=out['disp_postp'], eval_disp=out['disp_postp'],
+                          disp_slot=runner.pipes[ctx].disp_slot if stereo or from_head else None, host=host, slot=slot)
+            if from_head:
+                filled = self._pinned(('disp_filled', id(runner), ctx, slot), (B,), torch.int32)
+                filled.copy_(out['disp_filled'], non_blocking=True)
+                holder.update(disp=out['disp_depth'], filled=filled, ext=ext)
+                if self.stereo_eval_map == 'depth':
+                    holder['eval_disp'] = out['disp_depth']
             return out
-        _, ev = runner.submit(a, right=b if stereo else None, disp_postp=None if stereo else b, post=post)
+        _, ev = runner.submit(a, right=b if stereo else None, disp_postp=None if stereo else b, post=post, ext=ext)
         cmc = self._cmc_submit(st, s, e) if getattr(self.tracker, 'with_cmc', False) else None
         self.timings['submit_s'] += time.perf_counter() - ts
         st['jobs'][ci] = dict(s=s, e=e, ev=ev, cmc=cmc, **holder)
@@ -769,8 +807,14 @@ class OCSORT_Disparity(nn.Module):
                 tb[i, :len(t)] = t.bboxes
                 tc[i] = len(t)
             stream = self._side_stream(dev)
+            if 'filled' in job:      # depth_source: the chunk's head-filled pixel counts arrived with its records
+                eh, ew = job['ext']
+                for i, k in enumerate(job['filled'][:e - s].tolist()):
+                    data_samples[s + i].set_metainfo(dict(disp_filled=int(k), disp_fill_ratio=k / float(eh * ew)))
             with torch.cuda.stream(stream):
                 job['disp'].record_stream(stream)
+                if job['eval_disp'] is not job['disp']:
+                    job['eval_disp'].record_stream(stream)
                 tbd, tcd = tb.to(dev, non_blocking=True), tc.to(dev, non_blocking=True)
                 d = self._box_depth(job['disp'], tbd, tcd, self.baseline, self.focal_length)[0]
                 cols = [d]
@@ -810,7 +854,16 @@ class OCSORT_Disp_Completion_V2(OCSORT_Disparity):
     right after the detector forward.  `disp_mask` may be among the inputs; as in the reference's predict path nothing
     reads it.  One deliberate difference: the reference's V2 shell hands the tracker boxes without depth, but the
     registered tracker (OCSORTTracker_Disparity) associates on depth, so this shell keeps OCSORT_Disparity's per-box
-    depth from `disp_postp`."""
+    depth from `disp_postp`.
+
+    depth_source='input' | 'completed' | 'fused' (default 'input': everything as above).  Otherwise the per-box depths -
+    the detections' depths and scales the tracker associates on, and the tracks' `depth` column - are read from
+    `disp_depth`, the head's prediction at the padded input size ('fused': disp_postp wherever it is > 0, the head in its
+    holes; one st_disp_fuse launch per chunk), and every sample's metainfo gets `disp_filled`, the pixels of its
+    img_shape extent that came from the head, and `disp_fill_ratio` = disp_filled / (h * w).  `gt_depth` and
+    `dense_depth_map` are unaffected.  stereo_eval=dict(..., map='depth') scores `disp_depth` instead of disp_postp."""
+
+    _has_disp_head = True
 
     def __init__(self, detector=None, **kwargs):
         super().__init__(detector=detector, **kwargs)
@@ -818,16 +871,14 @@ class OCSORT_Disp_Completion_V2(OCSORT_Disparity):
             raise TypeError('OCSORT_Disp_Completion_V2 needs a YOLOX_DISP_Completion_V2 detector')
 
     def _runner_extras(self):     # the checkpoint's `detector.disp_head.*` are the pipeline's `disp_head.*`
-        return dict(disp_head=self.detector.head_config())
+        extras = dict(disp_head=self.detector.head_config())
+        if self.depth_source != 'input':
+            extras['depth_source'] = self.depth_source
+        return extras
 
     def _chunk_post(self, st, ci, pipe, out, s, e):
-        metas = [st['data_samples'][n].metainfo for n in range(s, e)]
-        # img_shape as the reference's predict requires it; a sample without one is taken at its un-padded frame size
-        shapes = {tuple(int(v) for v in (m.get('img_shape') or m['pad_shape'])[:2]) for m in metas}
-        if len(shapes) != 1:
-            raise NotImplementedError('dense_depth_map over a chunk needs one img_shape')
         # a tensor of the chunk's own: the context's buffers are overwritten by its next chunk
-        st.setdefault('dense', {})[ci] = pipe.disp_head.resize(out['dense_disp'], shapes.pop())
+        st.setdefault('dense', {})[ci] = pipe.disp_head.resize(out['dense_disp'], self._chunk_img_shape(st, s, e))
 
     def finish(self, st, lookahead=None):
         outs = super().finish(st, lookahead)       # has waited for every chunk's event

@@ -176,16 +176,25 @@ class MultiStreamTracker:
         d = self._device_state(dev)
         A = d['stream']
         jobs = []
+        # a model with depth_source other than 'input': the track boxes' depth is read from the chunk's disp_depth, as
+        # the detections' was (a slot of the disparity ring in both input configurations)
+        from_head = getattr(model, 'depth_source', 'input') != 'input'
         for ci in range(nc):
             s, e = ci * B, min(n, ci * B + B)
             a, b = shell_inputs.chunk_inputs(model, img, second, stereo, s, e, B, runner)
             job = dict(s=s, e=e)
+            ext = None
+            if from_head:
+                h, w = model._chunk_img_shape(dict(data_samples=samples), s, e)
+                ext = (min(h, runner.height), min(w, runner.width))
 
             def post(out, ctx, job=job):      # under the context's stream: the chunk's frame records, a tensor of their own
                 job.update(ctx=ctx, rec=runner.pipes[ctx].pack_detections(out, scaled='both', n_real=job['e'] - job['s']),
-                           disp=out['disp_postp'], disp_slot=runner.pipes[ctx].disp_slot if stereo else None)
+                           disp=out['disp_depth'] if from_head else out['disp_postp'],
+                           disp_slot=runner.pipes[ctx].disp_slot if stereo or from_head else None)
                 return out
-            job['ev'] = runner.submit(a, right=b if stereo else None, disp_postp=None if stereo else b, post=post)[1]
+            job['ev'] = runner.submit(a, right=b if stereo else None, disp_postp=None if stereo else b, post=post,
+                                      ext=ext)[1]
             jobs.append(job)
 
         slot_stream = np.full(nc * B, -1, np.int32)

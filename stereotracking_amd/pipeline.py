@@ -31,6 +31,19 @@ def depth_method_code(name):
     return DEPTH_METHODS[name]
 
 
+# where box_depth() reads its disparity (include/stereotrack.h st_disp_fuse `mode`): the input map disp_postp, the
+# disparity-completion head's prediction resized to the padded input, or the input with its invalid pixels (<= 0, NaN)
+# taken from the head
+DEPTH_SOURCES = {'input': 0, 'completed': 1, 'fused': 2}
+
+
+def depth_source_code(name):
+    """st_disp_fuse mode of a depth_source name (0: no launch); ValueError for anything else."""
+    if not isinstance(name, str) or name not in DEPTH_SOURCES:
+        raise ValueError(f'unknown depth_source {name!r}: one of {", ".join(DEPTH_SOURCES)}')
+    return DEPTH_SOURCES[name]
+
+
 def launch_box_depth(lib, disp, boxes, counts, baseline, focal, method, out, channel_stride):
     """ONE st_box_depth launch (st_box_depth_method for method != 0) on the current stream: disp (N,C,H,W) fp32, frames
     `channel_stride` floats apart, boxes (N,M,4), counts (N,) -> out = (depth, scales, scaled boxes), every row defined."""
@@ -118,7 +131,8 @@ class StereoDensePipeline:
                  stereo=True, max_disp=192, feat_stride=4, temperature=32.0, score_thr=0.01, iou_thr=0.5,
                  max_det=1000, baseline=0.25, focal_length=640, pad_size_divisor=32, agg_layers=0, agg3d_layers=0,
                  split_bf16=None, multi_label=True, rgb_only=False, full_res=False, full_res_channels=8, sgbm=None,
-                 depth_method='reference', lr_check=False, lr_max_diff=1.0, disp_head=None):
+                 depth_method='reference', lr_check=False, lr_max_diff=1.0, disp_head=None,
+                 depth_source='input'):
         """max_det: rows of the fixed-size detection buffer per frame.  The reference applies NO cap on the
         kept boxes (yolox_style=True => max_per_img = len(results)), so this is a
         capacity, not a threshold: `run()` reports `overflow` whenever a frame kept more boxes than fit, and
@@ -139,7 +153,18 @@ class StereoDensePipeline:
         The detector plan is then built with out_fd; the head runs on the context's stream right after the detector
         forward, on the 'p3' and 'stage1_disp' taps in the context's workspace (so before that workspace is reused), and
         `run()` also returns `dense_disp` (N,1,H/2,W/2), the completed disparity of the PADDED input at half resolution.
-        Parameters: `disp_head.*`.  None: nothing changes."""
+        Parameters: `disp_head.*`.  None: nothing changes.
+
+        depth_source: 'input' (box_depth reads disp_postp; no buffer, no launch), or - with disp_head - 'completed' /
+        'fused': one st_disp_fuse launch between the head and box_depth builds `disp_depth` (N,1,H,W), the head's
+        prediction resized to the PADDED input (the pixels disp_postp and the boxes live in), 'fused' keeping disp_postp
+        wherever it is > 0; box_depth reads that map, and `run()` also returns it and `disp_filled` (N,) int32, the
+        pixels inside `ext` that came from the head.  The map rotates over the `disp_buffers` slots under `disp_guard`
+        exactly like the stereo module's disp_postp: a consumer may read run k's map while run k + 1 is enqueued."""
+        self.depth_source = str(depth_source)
+        self._depth_src = depth_source_code(depth_source)
+        if self._depth_src and disp_head is None:
+            raise ValueError(f'depth_source={depth_source!r} reads the disparity-completion head: pass disp_head=')
         self.depth_method = str(depth_method)
         self._depth_code = depth_method_code(depth_method)
         self.lib = _lib.load()
@@ -220,7 +245,7 @@ class StereoDensePipeline:
         import os
         key = (f'v{self.det.lib.st_version()}_b{self.batch}_{self.height}x{self.width}_w{self.det.widen_factor:g}'
                f'_d{self.det.deepen_factor:g}_s{int(self.stereo)}{"r" if self.rgb_only else ""}'
-               f'{"f" if self.det.out_fd else ""}_a{self.agg_layers}'
+               f'{"f" if self.det.out_fd else ""}{"_ds%d" % self._depth_src if self._depth_src else ""}_a{self.agg_layers}'
                f'_D{self.max_disp // self.feat_stride if self.full_res else self.D}'
                f'{"_F%d" % self.stereo_module.reduce.out_channels if self.full_res else ""}'
                f'_ops{self.det.lib.st_detector_num_ops(self.det.handle)}_{_device_tag()}'
@@ -290,6 +315,9 @@ class StereoDensePipeline:
             b['overflow'] = torch.empty(N, dtype=torch.bool, device=dev)
             if self.disp_head is not None:
                 b['dense_disp'] = torch.empty(N, 1, H // 2, W // 2, **f32)
+            if self._depth_src:     # one map (and its counters) per disparity slot, under the same guard events
+                b['depth_ring'] = [torch.empty(N, 1, H, W, **f32) for _ in b['disp_ring']]
+                b['filled_ring'] = [torch.empty(N, dtype=torch.int32, device=dev) for _ in b['disp_ring']]
             self._bufs = b
         return self._bufs
 
@@ -313,6 +341,28 @@ class StereoDensePipeline:
             self.stereo_module.compute(self.det, img, right, (self.ori_h, self.ori_w), b['disp_lr'], out, disp_mask=mask)
         return out
 
+    def depth_map(self, disp_postp, ext=None):
+        """st_disp_fuse: the head's `dense_disp` of this run (+ plane 0 of disp_postp) -> disp_depth (N,1,H,W), filled (N,).
+        The stereo / SGBM pipeline writes the slot disparity() just took (its guard has been waited for); the mono
+        pipeline, whose disp_postp is the caller's tensor, takes the next slot here."""
+        b = self._buffers(disp_postp.device)
+        N, H, W = self.batch, self.height, self.width
+        if tuple(disp_postp.shape[-2:]) != (H, W) or disp_postp.shape[0] != N or not disp_postp.is_contiguous():
+            raise ValueError(f'disp_postp: expected a contiguous ({N}, C, {H}, {W}) map, got {tuple(disp_postp.shape)}')
+        if not self.takes_right:
+            k = self._disp_turn % len(b['depth_ring'])
+            self._disp_turn += 1
+            self.disp_slot = k
+            if self.disp_guard[k] is not None:
+                torch.cuda.current_stream(disp_postp.device).wait_event(self.disp_guard[k])
+                self.disp_guard[k] = None
+        k = self.disp_slot
+        eh, ew = (self.ori_h, self.ori_w) if ext is None else (int(ext[0]), int(ext[1]))
+        out, filled = b['depth_ring'][k], b['filled_ring'][k]
+        check(self.lib.st_disp_fuse(ptr(b['dense_disp']), ptr(disp_postp), disp_postp.shape[1] * H * W, N, H, W, eh, ew,
+                                    self._depth_src, ptr(out), ptr(filled), current_stream()), 'st_disp_fuse')
+        return out, filled
+
     def box_depth(self, disp_postp, boxes, counts, out=None):
         """bbox_postp_depth (ocsort_disparity.py:113-130) on device -> depth, scales, scaled boxes."""
         b = self._buffers(disp_postp.device)
@@ -322,13 +372,14 @@ class StereoDensePipeline:
                          Cc * H * W)
         return out
 
-    def run(self, img, right=None, disp_postp=None):
+    def run(self, img, right=None, disp_postp=None, ext=None):
         """img (N,3,H,W) fp32 CUDA; stereo: right (N,3,H,W); mono: disp_postp (N,3,H,W).  img (and, stereo, right)
         may be engine.RawChunk (N uint8 frames each): the stem kernels cast + pad them while staging their windows.
         Returns a dict of device tensors (no host sync; the context's PERSISTENT buffers, overwritten by its next run): boxes (N,M,4) unscaled xyxy, scores, labels,
         prior_idx, counts (TRUE number kept per frame), overflow (N,) bool = counts > M, depth, scales,
         scaled_boxes, disp_postp, head (and, with lr_check, disp_mask (N,1,H,W): 1 = valid).  Rows past min(counts, M) are zero (prior_idx -1).  With disp_buffers > 1 the
-        stereo module's disp_postp is buffer `self.disp_slot` of the ring (see _buffers)."""
+        stereo module's disp_postp is buffer `self.disp_slot` of the ring (see _buffers).  ext: (h, w) of the frames inside
+        the padded input (img_shape; default ori_shape) - with a depth_source other than 'input', where `disp_filled` counts."""
         if isinstance(img, RawChunk):
             if (self.stereo or self.sgbm is not None) and not isinstance(right, RawChunk):
                 raise ValueError('the stereo pipeline takes left AND right as raw uint8 chunks (or both as fp32 tensors)')
@@ -353,7 +404,10 @@ class StereoDensePipeline:
             self.disp_head.forward(self.det, out=b['dense_disp'])
         boxes, scores, labels, prior, counts = self.det.decode_nms(
             b['head'], self.score_thr, self.iou_thr, self.max_det, (self.ori_h, self.ori_w), out=b['decode'])
-        depth, scales, sboxes = self.box_depth(disp_postp, boxes, counts)
+        disp_depth = filled = None
+        if self._depth_src:
+            disp_depth, filled = self.depth_map(disp_postp, ext)
+        depth, scales, sboxes = self.box_depth(disp_postp if disp_depth is None else disp_depth, boxes, counts)
         torch.gt(counts, self.max_det, out=b['overflow'])
         out = dict(boxes=boxes, scores=scores, labels=labels, prior_idx=prior, counts=counts,
                    overflow=b['overflow'], depth=depth, scales=scales, scaled_boxes=sboxes,
@@ -362,6 +416,8 @@ class StereoDensePipeline:
             out['disp_mask'] = b['disp_mask']
         if self.disp_head is not None:
             out['dense_disp'] = b['dense_disp']
+        if disp_depth is not None:
+            out['disp_depth'], out['disp_filled'] = disp_depth, filled
         return out
 
     @staticmethod
@@ -407,7 +463,8 @@ class InflightPipelines:
 
     def __getattr__(self, name):   # geometry / thresholds of the (identical) contexts: batch, max_det, stereo, ...
         if name in ('batch', 'max_det', 'stereo', 'height', 'width', 'ori_h', 'ori_w', 'agg_layers', 'agg3d_layers', 'split_bf16',
-                    'rgb_only', 'full_res', 'sgbm', 'takes_right', 'depth_method', 'lr_check', 'lr_max_diff', 'disp_head'):
+                    'rgb_only', 'full_res', 'sgbm', 'takes_right', 'depth_method', 'lr_check', 'lr_max_diff', 'disp_head',
+                    'depth_source'):
             return getattr(self.pipes[0], name)
         raise AttributeError(name)
 
@@ -430,9 +487,9 @@ class InflightPipelines:
             self.streams = [torch.cuda.Stream(device=device) for _ in self.pipes]
         return self.streams[self._next % len(self.pipes)]
 
-    def submit(self, img, right=None, disp_postp=None, post=None):
+    def submit(self, img, right=None, disp_postp=None, post=None, ext=None):
         """Enqueue one batch on the next context's stream (after everything already enqueued on the caller's
-        current stream, where the inputs were produced).  `post(out)` runs under that stream too."""
+        current stream, where the inputs were produced).  `post(out)` runs under that stream too.  ext: run()'s."""
         if not isinstance(img, RawChunk):
             _require_cuda(img, 'img')
         if self.streams is None:
@@ -445,7 +502,7 @@ class InflightPipelines:
             if t is not None:
                 t.record_stream(s)
         with torch.cuda.stream(s):
-            out = self.pipes[j].run(img, right, disp_postp)
+            out = self.pipes[j].run(img, right, disp_postp, ext)
             if post is not None:
                 out = post(out, j)
             ev = torch.cuda.Event()

@@ -327,6 +327,10 @@ def track_gathered(dets, counts, num_frames, tracker, model):
     if getattr(model, 'stereo_eval', None) is not None:
         raise NotImplementedError('stereo_eval (the dense disparity evaluator) is not wired into the sharded driver; '
                                   'run the video through OCSORT_Disparity.predict on one device')
+    if getattr(model, 'depth_source', 'input') != 'input':
+        raise NotImplementedError(f'depth_source={model.depth_source!r} (per-box depth from the completed disparity) is '
+                                  f'not wired into the sharded driver; run the video through '
+                                  f'OCSORT_Disp_Completion_V2.predict on one device')
     dets = dets.cpu()
     results = []
     for t in range(num_frames):
