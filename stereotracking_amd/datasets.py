@@ -183,9 +183,10 @@ class MOTDispDataset:
         prefix = self.data_prefix.get('img_path')
         img_path = os.path.join(prefix, fname) if prefix is not None else fname
         info['img_path'] = img_path
-        info['disp_path'] = img_path.replace(fname, fname.replace('left', self.disparity_dir_name))
+        # '.jpg' -> '.png': JPEG camera frames sit beside PNG disparity / depth maps (the rule of selma_dataset.py:42-46)
+        info['disp_path'] = img_path.replace(fname, fname.replace('left', self.disparity_dir_name)).replace('.jpg', '.png')
         if self.depth_dir_name is not None:
-            info['depth_path'] = img_path.replace(fname, fname.replace('left', self.depth_dir_name))
+            info['depth_path'] = img_path.replace(fname, fname.replace('left', self.depth_dir_name)).replace('.jpg', '.png')
         info['right_path'] = img_path.replace(fname, fname.replace('left', self.right_dir_name))
         instances = []
         for ann in ann_info:
@@ -252,7 +253,7 @@ class MOTKittiDataset(MOTDispDataset):
         prefix = self.data_prefix.get('img_path')
         img_path = os.path.join(prefix, fname) if prefix is not None else fname
         info['img_path'] = img_path
-        info['disp_path'] = img_path.replace(fname, fname.replace('img2', self.disparity_dir_name))
+        info['disp_path'] = img_path.replace(fname, fname.replace('img2', self.disparity_dir_name)).replace('.jpg', '.png')
         info['right_path'] = img_path.replace(fname, fname.replace('img2', self.right_dir_name))
         instances = []
         for ann in ann_info:
@@ -303,13 +304,33 @@ class VideoSampler:
 # ---- test-time transforms ------------------------------------------------------------------------------------------
 @TRANSFORMS.register_module(name=['LoadImageFromFile', 'mmcv.LoadImageFromFile'])
 class LoadImageFromFile:
-    """mmcv LoadImageFromFile [upstream-memory]: uint8 (h,w,3) in BGR order (OpenCV's), img_shape / ori_shape set."""
+    """mmcv LoadImageFromFile [upstream-memory]: uint8 (h,w,3) in BGR order (OpenCV's), img_shape / ori_shape set.
+    The format is sniffed from the file's first bytes, as mmcv.imfrombytes does not care either: PNG (read_png) or JPEG
+    (jpeg.read_jpeg, the host decoder).  decode='defer': a JPEG is not decoded here - its bytes are kept under
+    `out + '_bytes'` (for jpeg.JpegDecoder, which decodes batches on the device) and the shapes come from its header."""
 
-    def __init__(self, to_float32=False, key='img_path', out='img', **kwargs):
-        self.to_float32, self.key, self.out = to_float32, key, out
+    def __init__(self, to_float32=False, key='img_path', out='img', decode='host', **kwargs):
+        if decode not in ('host', 'defer'):
+            raise ValueError("decode is 'host' or 'defer'")
+        self.to_float32, self.key, self.out, self.decode = to_float32, key, out, decode
 
     def __call__(self, results):
-        img = read_png(results[self.key])
+        data = results[self.key]
+        if not isinstance(data, (bytes, bytearray, memoryview)):
+            with open(data, 'rb') as f:
+                data = f.read()
+        if bytes(data[:2]) == b'\xff\xd8':
+            from . import jpeg
+            data = bytes(data)
+            if self.decode == 'defer':
+                info = jpeg.jpeg_info(data)
+                results[self.out + '_bytes'] = data
+                if self.out == 'img':
+                    results['img_shape'] = results['ori_shape'] = (info['height'], info['width'])
+                return results
+            img = jpeg.read_jpeg(data)
+        else:
+            img = read_png(data)         # anything else: ValueError('not a PNG file')
         if img.ndim == 2:
             img = np.repeat(img[..., None], 3, -1)
         img = np.ascontiguousarray(img[..., 2::-1])       # stored RGB(A) -> BGR

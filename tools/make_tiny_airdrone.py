@@ -9,7 +9,9 @@ PNG decode -> raw-byte upload -> dense path -> tracker -> MOTDroneMetrics - can 
                                                                             (tools/dataset_converters/AirSim_drone/convertAnnToCocoFormat.py:49-191)
 Encodings: disparity PNG = 16 * px, 65535 = invalid (loading_disparity.py:82,129-134); depth PNG = 100 * metres (:233).
 The PNG writer cycles through all five scanline filters, so reading the dataset exercises the whole decoder.
-usage: python tools/make_tiny_airdrone.py <root> [--videos 3 --frames 12 --height 96 --width 160]"""
+--jpeg: the left / right images are written as %06d.jpg (jpeg.write_jpeg, quality 90, 4:2:0, a restart marker per MCU
+row), the way the reference's JPEG datasets store camera frames; disparity and depth stay PNG (a lossy code is no code).
+usage: python tools/make_tiny_airdrone.py <root> [--videos 3 --frames 12 --height 96 --width 160 --jpeg]"""
 import argparse
 import json
 import os
@@ -22,8 +24,9 @@ sys.path.insert(0, ROOT)
 
 
 def make(root, videos=3, frames=12, height=96, width=160, max_disp=32, objects=3, seed=0, distance_thr=80.0,
-         area_thr=30.0):
+         area_thr=30.0, jpeg=False):
     from stereotracking_amd.datasets import write_png
+    from stereotracking_amd.jpeg import write_jpeg
     from stereotracking_amd.sequence import synthetic_sequence
     base = os.path.join(root, 'AirSim_drone')
     os.makedirs(os.path.join(base, 'annotations'), exist_ok=True)
@@ -40,8 +43,14 @@ def make(root, videos=3, frames=12, height=96, width=160, max_disp=32, objects=3
         for t, f in enumerate(synthetic_sequence(frames, objects, height, width, max_disp, seed=seed + v)):
             fn = f'{t:06d}.png'
             filt = [(y + t) % 5 for y in range(height)]
-            write_png(os.path.join(vdir, 'left', fn), f['left'][::-1].transpose(1, 2, 0), filters=filt)    # BGR -> RGB
-            write_png(os.path.join(vdir, 'right', fn), f['right'][::-1].transpose(1, 2, 0), filters=filt)
+            img_fn = f'{t:06d}.jpg' if jpeg else fn
+            for side in ('left', 'right'):
+                rgb = np.ascontiguousarray(f[side][::-1].transpose(1, 2, 0))                   # BGR -> RGB
+                if jpeg:
+                    write_jpeg(os.path.join(vdir, side, img_fn), rgb, quality=90, subsampling='420',
+                               restart_interval=(width + 15) // 16)
+                else:
+                    write_png(os.path.join(vdir, side, img_fn), rgb, filters=filt)
             codes = (f['disp'] * 16.0).astype(np.uint16)
             y0, x0 = rng.randint(0, height - 8), rng.randint(0, width - 8)
             codes[y0:y0 + 6, x0:x0 + 6] = 65535                                      # an invalid patch
@@ -49,7 +58,7 @@ def make(root, videos=3, frames=12, height=96, width=160, max_disp=32, objects=3
             depth_m = 0.25 * 640.0 / np.maximum(f['disp'], 1e-3)
             write_png(os.path.join(vdir, 'depth', fn), np.clip(np.rint(depth_m * 100.0), 0, 65535).astype(np.uint16),
                       filters=filt)
-            out['images'].append(dict(id=img_id, video_id=vid_id, file_name=os.path.join(name, 'left', fn),
+            out['images'].append(dict(id=img_id, video_id=vid_id, file_name=os.path.join(name, 'left', img_fn),
                                       height=height, width=width, frame_id=t, mot_frame_ids=t + 1))
             for k, x1, y1, x2, y2, z in f['gt']:
                 bbox = [float(x1), float(y1), float(x2 - x1), float(y2 - y1)]
@@ -83,5 +92,6 @@ if __name__ == '__main__':
     ap.add_argument('--frames', type=int, default=12)
     ap.add_argument('--height', type=int, default=96)
     ap.add_argument('--width', type=int, default=160)
+    ap.add_argument('--jpeg', action='store_true', help='left / right images as JPEG (disparity and depth stay PNG)')
     a = ap.parse_args()
-    print(make(a.root, a.videos, a.frames, a.height, a.width))
+    print(make(a.root, a.videos, a.frames, a.height, a.width, jpeg=a.jpeg))
