@@ -44,6 +44,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._packed import PackedCall
 from .metrics import _check_backend
 from .registry import TASK_UTILS
 from .tracklets import _as_rows, _finish, _sorted_tracks
@@ -334,16 +335,8 @@ class AppearanceFreeLink:
         return self._device_weights[key]
 
     def _forward_many_device(self, row_arrays, device, budget, timing):
-        t_start = time.perf_counter()
-        if not torch.cuda.is_available():
-            raise RuntimeError('the device backend of AppearanceFreeLink runs on the HIP path only (csrc/aflink.hip) and '
-                               'no CUDA (ROCm) device is available; use backend=\'host\'')
-        lib = _lib.load()
-        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        if dev.type != 'cuda':
-            raise RuntimeError(f'the device backend of AppearanceFreeLink needs a CUDA (ROCm) device, got {dev}')
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
+        call = PackedCall('AppearanceFreeLink', 'csrc/aflink.hip', device, timing, LAUNCHES)
+        lib, dev = call.lib, call.dev
         budget = WORKSPACE_BUDGET_BYTES if budget is None else int(budget)
         p = self.plan(row_arrays)
         B, T, cap = len(row_arrays), p['T'], p['capacity']
@@ -356,58 +349,30 @@ class AppearanceFreeLink:
                              f'budget is {budget}')
         if T == 0 or cap == 0:
             out = [link_from_scores(t, np.zeros((0, 2)), np.zeros(0), self.confidence_threshold) for t in p['tracks']]
-            return (out, dict(stages_ms={}, candidates=0, host_prepare_s=time.perf_counter() - t_start)) if timing else out
+            return (out, dict(stages_ms={}, candidates=0, host_prepare_s=time.perf_counter() - call.t_start)) if timing else out
         weights = self.device_weights(dev)
 
-        from .mot_eval import _Layout
-        host_in = {k: p[k] for k in ('feat', 'trk_off', 'trk_set', 'set_off')}
-        lin = _Layout()
-        for k, v in host_in.items():
-            lin.add(k, v.shape, v.dtype)
-        hbuf = np.zeros(lin.size, np.uint8)
-        for k, v in host_in.items():
-            lin.view(hbuf, k)[...] = v
-        lout = _Layout()
-        lout.add('header', (2,), np.int32)
-        lout.add('cand', (cap, 3), np.int32)
-        lout.add('conf', (cap,), np.float32)
-        t_prep = time.perf_counter()
-
-        dbuf = torch.from_numpy(hbuf).to(dev)                                # the one upload
-        obuf = torch.empty(lout.size, dtype=torch.uint8, device=dev)
+        call.upload({k: p[k] for k in ('feat', 'trk_off', 'trk_set', 'set_off')})
+        call.outputs((('header', (2,), np.int32), ('cand', (cap, 3), np.int32), ('conf', (cap,), np.float32)))
         ws_off = torch.empty(T + 1, dtype=torch.int32, device=dev)
         ws_x = torch.empty(chunk * 2 * LENGTH * 3, dtype=torch.float32, device=dev)
         args = self._args(p, cap, chunk)
-        for k in host_in:
-            setattr(args, k, C.c_void_p(dbuf.data_ptr() + lin.items[k][0]))
-        for k in lout.items:
-            setattr(args, k, C.c_void_p(obuf.data_ptr() + lout.items[k][0]))
+        call.bind(args)
         args.ws_off, args.ws_x = C.c_void_p(ws_off.data_ptr()), C.c_void_p(ws_x.data_ptr())
-        with torch.cuda.device(dev):
-            stream = _lib.current_stream()
-            events = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing else None
-            if timing:
-                events[0].record()
-            LAUNCHES['st_aflink_run'] += 1
-            _lib.check(lib.st_aflink_run(C.byref(args), weights.handle, stream), 'st_aflink_run')
-            if timing:
-                events[1].record()
-        host = obuf.cpu().numpy()              # the one wait and the one copy back
-        t_back = time.perf_counter()
-        header = lout.view(host, 'header')
+        with call.stages():
+            call.launch('st_aflink_run', C.byref(args), weights.handle)
+        host = call.fetch()
+        header = host['header']
         if header[1] or header[0] > cap:
             raise _lib.StError(f'AppearanceFreeLink: the device reports status {int(header[1])} with {int(header[0])} '
                                f'candidates in {cap} slots: the host tables and the buffers disagree')
         n = int(header[0])
-        cand, conf = lout.view(host, 'cand')[:n], lout.view(host, 'conf')[:n]
+        cand, conf = host['cand'][:n], host['conf'][:n]
         set_off = np.searchsorted(cand[:, 0], np.arange(B + 1))
         out = [link_from_scores(p['tracks'][s], cand[set_off[s]:set_off[s + 1], 1:], conf[set_off[s]:set_off[s + 1]],
                                 self.confidence_threshold) for s in range(B)]
         if timing:
-            t_end = time.perf_counter()
-            return out, dict(stages_ms={'st_aflink_run': events[0].elapsed_time(events[1])}, candidates=n, capacity=cap,
-                             rounds=-(-cap // chunk), tracks=T, rows_in=p['R'], host_prepare_s=t_prep - t_start,
-                             device_and_copies_s=t_back - t_prep, host_finish_s=t_end - t_back, total_s=t_end - t_start)
+            return out, call.timing_dict(candidates=n, capacity=cap, rounds=-(-cap // chunk), tracks=T, rows_in=p['R'])
         return out
 
     def _args(self, p, capacity, chunk):

@@ -25,13 +25,13 @@ Both backends are defined up to ties of the assignment optimum (DESIGN.md sectio
 """
 import collections
 import ctypes as C
-import time
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import StMotArgs, check, current_stream
+from ._packed import PackedCall
 
 ST_MOT_CLEAR, ST_MOT_HOTA = 1, 2
 STATUS_KINDS = ((1, 'a non-finite box'), (2, 'an id that occurs twice in one frame'), (4, 'rows that are not sorted by frame'),
@@ -83,36 +83,20 @@ def pack_sequences(gt_by_video, pred_by_video):
     if not isinstance(pred_by_video, dict):
         pred_by_video = dict(enumerate(pred_by_video))
     videos = sorted(set(gt_by_video) | set(pred_by_video))
-    gt_parts, pr_parts, frame_no, frame_seq, fg, fp_ = [], [], [], [], [0], [0]
-    seq_frame_off, seq_ng, seq_nt, gt_ids, tr_ids = [0], [], [], [], []
-    ngt = npr = 0
-    for s, v in enumerate(videos):
+    srt, seq_ng, seq_nt, gt_ids, tr_ids = [], [], [], [], []
+    for v in videos:
         g, gfr, gu = _sort_and_compact(_rows6(gt_by_video.get(v, ())), v, 'ground-truth')
         p, pfr, pu = _sort_and_compact(_rows6(pred_by_video.get(v, ())), v, 'prediction')
-        frames = np.union1d(gfr, pfr)
-        gt_parts.append(g)
-        pr_parts.append(p)
-        frame_no.append(frames)
-        frame_seq.append(np.full(len(frames), s, np.int32))
-        fg.append(ngt + np.searchsorted(gfr, frames, 'right'))
-        fp_.append(npr + np.searchsorted(pfr, frames, 'right'))
-        ngt, npr = ngt + len(g), npr + len(p)
-        seq_frame_off.append(seq_frame_off[-1] + len(frames))
+        srt.append([(g, gfr, None), (p, pfr, None)])
         seq_ng.append(len(gu))
         seq_nt.append(len(pu))
         gt_ids.append(gu)
         tr_ids.append(pu)
-    if max(ngt, npr, seq_frame_off[-1]) >= 2 ** 31 - 1:
-        raise ValueError(f'pack_sequences: {ngt} ground-truth rows, {npr} prediction rows, {seq_frame_off[-1]} frames: the '
-                         f'offset tables are 32-bit')
-    out = dict(videos=videos, gt_ids=gt_ids, tr_ids=tr_ids)
-    out['gt_rows'] = np.ascontiguousarray(np.concatenate(gt_parts)) if videos else np.zeros((0, 6))
-    out['pred_rows'] = np.ascontiguousarray(np.concatenate(pr_parts)) if videos else np.zeros((0, 6))
-    out['seq_frame_off'] = np.asarray(seq_frame_off, np.int32)
-    out['frame_seq'] = np.concatenate(frame_seq + [np.zeros(0, np.int32)]).astype(np.int32)
-    out['frame_no'] = np.concatenate(frame_no + [np.zeros(0, np.int64)]).astype(np.int64)
-    out['frame_gt_off'] = np.concatenate([np.atleast_1d(a) for a in fg]).astype(np.int32)
-    out['frame_pred_off'] = np.concatenate([np.atleast_1d(a) for a in fp_]).astype(np.int32)
+    t = _frame_tables(srt, (6, 6), lambda totals, F: f'pack_sequences: {totals[0]} ground-truth rows, {totals[1]} prediction '
+                                                     f'rows, {F} frames: the offset tables are 32-bit')
+    out = dict(videos=videos, gt_ids=gt_ids, tr_ids=tr_ids, frame_seq=t['frame_seq'], frame_no=t['frame_no'])
+    (out['gt_rows'], out['pred_rows']), (out['frame_gt_off'], out['frame_pred_off']) = t['rows'], t['offs']
+    out['seq_frame_off'] = np.searchsorted(t['frame_seq'], np.arange(len(videos) + 1)).astype(np.int32)
     G, P = np.diff(out['frame_gt_off']).astype(np.int64), np.diff(out['frame_pred_off']).astype(np.int64)
     out['frame_pair_off'] = np.concatenate([[0], np.cumsum(G * P)]).astype(np.int64)
     out['seq_ng'], out['seq_nt'] = np.asarray(seq_ng, np.int32), np.asarray(seq_nt, np.int32)
@@ -120,50 +104,23 @@ def pack_sequences(gt_by_video, pred_by_video):
     out['seq_gid_off'] = np.concatenate([[0], np.cumsum(ng)]).astype(np.int64)
     out['seq_tid_off'] = np.concatenate([[0], np.cumsum(nt)]).astype(np.int64)
     out['seq_mat_off'] = np.concatenate([[0], np.cumsum(ng * nt)]).astype(np.int64)
-    out['max_frame_objects'] = int(max(G.max(initial=0), P.max(initial=0)))
+    out['max_frame_objects'] = t['max_frame_objects']
     return out
 
 
-class _Layout:
-    """Arrays side by side in one byte buffer, every one at a multiple of 256 bytes."""
-
-    def __init__(self):
-        self.items, self.size = {}, 0
-
-    def add(self, name, shape, dtype):
-        dtype = np.dtype(dtype)
-        n = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
-        self.items[name] = (self.size, tuple(int(v) for v in shape), dtype)
-        self.size += (n + 255) // 256 * 256 + 256
-
-    def view(self, buf, name):
-        off, shape, dtype = self.items[name]
-        n = int(np.prod(shape, dtype=np.int64))
-        return buf[off:off + n * dtype.itemsize].view(dtype).reshape(shape)
-
-
-def _device_view(layout, buf, name):
-    """_Layout.view for the device copy of the buffer (a uint8 tensor)."""
-    off, shape, dtype = layout.items[name]
-    n = int(np.prod(shape, dtype=np.int64))
-    return buf[off:off + n * dtype.itemsize].view(getattr(torch, dtype.name)).view(shape)
-
-
-def _where(packed, status, kind):
-    f = int(packed['frame_no'].shape[0]) - int(status[1 + kind])
-    return packed['videos'][int(packed['frame_seq'][f])], int(packed['frame_no'][f])
-
-
-def _raise_status(packed, status):
+def _raise_status(prefix, kinds, status, videos, frame_seq, frame_no, limit=''):
+    """A non-zero device status word as an exception.  kinds: (bit, text) of every condition the entry reports, the first
+    set one is raised; the status holds, in word 1 + the bit's position, the number of frames minus the first frame
+    that has it.  limit: the note of bit 8, '{n}' = max_frame_objects()."""
     bits = int(status[0])
-    for kind, (bit, what) in enumerate(STATUS_KINDS):
+    for bit, what in kinds:
         if bits & bit:
-            video, frame = _where(packed, status, kind)
-            msg = f'MOT evaluation: {what}: video {video!r}, frame {frame}'
+            f = len(frame_no) - int(status[bit.bit_length()])
+            msg = f'{prefix}: {what}: video {videos[int(frame_seq[f])]!r}, frame {int(frame_no[f])}'
             if bit == 8:
-                msg += f' (at most {max_frame_objects()} ground-truth and {max_frame_objects()} prediction rows per frame)'
+                msg += limit.format(n=max_frame_objects())
             raise ValueError(msg) if bit in (1, 2, 8) else _lib.StError(msg)
-    raise _lib.StError(f'MOT evaluation failed on the device: status {bits}')
+    raise _lib.StError(f'{prefix} failed on the device: status {bits}')
 
 
 def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None, alphas=None, timing=False,
@@ -179,19 +136,13 @@ def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), 
     `device_boxes`: (gt (num_gt, 4), pred (num_pred, 4)) fp64 tensors on the device that replace the x, y, w, h columns
     of the packed rows after the upload (evaluate_motchallenge: boxes that never left the device)."""
     from . import metrics as M
-    t_start = time.perf_counter()
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
     do_hota = 'HOTA' in metrics
     do_clear = 'CLEAR' in metrics or 'Identity' in metrics
     if not (do_hota or do_clear):
         raise ValueError(f'evaluate_packed: nothing to compute for metrics {metrics}')
-    if not torch.cuda.is_available():
-        raise RuntimeError('the device backend of the MOT evaluation runs on the HIP path only (csrc/mot_eval.hip) and '
-                           'no CUDA (ROCm) device is available; use backend=\'host\'')
-    lib = _lib.load()
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise RuntimeError(f'the device backend of the MOT evaluation needs a CUDA (ROCm) device, got {dev}')
+    call = PackedCall('the MOT evaluation', 'csrc/mot_eval.hip', device, timing, LAUNCHES)
+    dev = call.dev
     alphas = np.ascontiguousarray(M.HOTA_ALPHAS if alphas is None else alphas, dtype=np.float64)
     B, F, A = len(packed['videos']), len(packed['frame_no']), len(alphas)
     if B == 0:
@@ -199,33 +150,19 @@ def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), 
     NG, NP_ = len(packed['gt_rows']), len(packed['pred_rows'])
     ids_g, ids_t, cells = int(packed['seq_gid_off'][-1]), int(packed['seq_tid_off'][-1]), int(packed['seq_mat_off'][-1])
 
-    # ---- one upload
-    lin = _Layout()
-    host_in = dict(gt_rows=packed['gt_rows'], pred_rows=packed['pred_rows'], alphas=alphas, **{k: packed[k] for k in _TABLES})
-    for k, v in host_in.items():
-        lin.add(k, v.shape, v.dtype)
-    hbuf = np.zeros(lin.size, np.uint8)
-    for k, v in host_in.items():
-        lin.view(hbuf, k)[...] = v
-    t_prep = time.perf_counter()
-    dbuf = torch.from_numpy(hbuf).to(dev)
+    call.upload(dict(gt_rows=packed['gt_rows'], pred_rows=packed['pred_rows'], alphas=alphas, **{k: packed[k] for k in _TABLES}))
     if device_boxes is not None:
         for name, boxes in zip(('gt_rows', 'pred_rows'), device_boxes):
-            off, (n, _), _ = lin.items[name]
+            n = len(packed[name])
             if tuple(boxes.shape) != (n, 4) or boxes.dtype != torch.float64 or boxes.device != dev:
                 raise ValueError(f'evaluate_packed: device_boxes for {name} must be ({n}, 4) float64 on {dev}')
             if n:
-                dbuf[off:off + n * 48].view(torch.float64).view(n, 6)[:, 2:6] = boxes
-
-    lout = _Layout()
-    for name, shape, dt in (('status', (8,), np.int32), ('gt_count', (ids_g,), np.int32), ('tr_count', (ids_t,), np.int32),
-                            ('id_potential', (cells,), np.int32), ('hota_potential', (cells,), np.float64),
-                            ('gt_frames', (ids_g,), np.int32), ('gt_matched', (ids_g,), np.int32),
-                            ('gt_frag', (ids_g,), np.int32), ('clear_counts', (B, 4), np.int32),
-                            ('motp_sum', (B,), np.float64), ('hota_counts', (B, A, 3), np.int32),
-                            ('hota_sums', (B, A, 4), np.float64)):
-        lout.add(name, shape, dt)
-    obuf = torch.zeros(lout.size, dtype=torch.uint8, device=dev)
+                call.device_in(name)[:, 2:6] = boxes
+    call.outputs((('status', (8,), np.int32), ('gt_count', (ids_g,), np.int32), ('tr_count', (ids_t,), np.int32),
+                  ('id_potential', (cells,), np.int32), ('hota_potential', (cells,), np.float64),
+                  ('gt_frames', (ids_g,), np.int32), ('gt_matched', (ids_g,), np.int32), ('gt_frag', (ids_g,), np.int32),
+                  ('clear_counts', (B, 4), np.int32), ('motp_sum', (B,), np.float64), ('hota_counts', (B, A, 3), np.int32),
+                  ('hota_sums', (B, A, 4), np.float64)), zero=True)
 
     args = StMotArgs()
     args.struct_size = C.sizeof(StMotArgs)
@@ -234,45 +171,26 @@ def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), 
     args.flags = (ST_MOT_CLEAR if do_clear else 0) | (ST_MOT_HOTA if do_hota else 0)
     args.num_pairs, args.num_cells, args.num_gids, args.num_tids = int(packed['frame_pair_off'][-1]), cells, ids_g, ids_t
     args.iou_thr = float(iou_thr)
-    for k in host_in:
-        setattr(args, k, C.c_void_p(dbuf.data_ptr() + lin.items[k][0]))
-    for k in lout.items:
-        setattr(args, k, C.c_void_p(obuf.data_ptr() + lout.items[k][0]))
-    args.ws, args.ws_bytes = None, 0
-    nbytes = int(lib.st_mot_workspace_bytes(C.byref(args)))
-    if nbytes == 0:
-        raise _lib.StError('st_mot_workspace_bytes: invalid sizes')
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    args.ws, args.ws_bytes = C.c_void_p(ws.data_ptr()), nbytes
+    call.bind(args)
+    call.workspace(args, call.workspace_bytes('st_mot_workspace_bytes', args))
 
-    stages = [('st_mot_similarity', lib.st_mot_similarity), ('st_mot_walk', lib.st_mot_walk)]
-    if do_hota:
-        stages += [('st_mot_hota_match', lib.st_mot_hota_match), ('st_mot_hota_accumulate', lib.st_mot_hota_accumulate)]
-    over_limit = False
-    with torch.cuda.device(dev):
-        stream = current_stream()
-        events = [torch.cuda.Event(enable_timing=True) for _ in range(len(stages) + 1)] if timing else None
-        for i, (name, fn) in enumerate(stages):
-            if timing:
-                events[i].record()
-            LAUNCHES[name] += 1
-            rc = fn(C.byref(args), stream)
-            if name == 'st_mot_similarity' and rc == -1 and args.max_frame_objects > max_frame_objects():
-                over_limit = True      # the checks were launched: the status word names the frame
-                break
-            check(rc, name)
-        if timing and not over_limit:
-            events[-1].record()
-    host = obuf.cpu().numpy()          # the one wait and the one copy back
-    t_back = time.perf_counter()
-    status = lout.view(host, 'status')
-    if status[0] or over_limit:
-        _raise_status(packed, status)
-    o = {k: lout.view(host, k) for k in lout.items}
+    # over the limit st_mot_similarity launches its checks and returns -1: the status word names the frame
+    over = args.max_frame_objects > max_frame_objects()
+    with call.stages():
+        over_limit = call.launch('st_mot_similarity', C.byref(args), ok=(0, -1) if over else (0,)) == -1
+        if not over_limit:
+            call.launch('st_mot_walk', C.byref(args))
+            if do_hota:
+                call.launch('st_mot_hota_match', C.byref(args))
+                call.launch('st_mot_hota_accumulate', C.byref(args))
+    o = call.fetch()
+    if o['status'][0] or over_limit:
+        _raise_status('MOT evaluation', STATUS_KINDS, o['status'], packed['videos'], packed['frame_seq'], packed['frame_no'],
+                      ' (at most {n} ground-truth and {n} prediction rows per frame)')
     sim = None
     if return_arrays:
-        off = int(lib.st_mot_workspace_sim_offset(C.byref(args)))
-        sim = ws[off:off + 8 * args.num_pairs].cpu().numpy().view(np.float64)
+        off = int(call.lib.st_mot_workspace_sim_offset(C.byref(args)))
+        sim = call.ws[off:off + 8 * args.num_pairs].cpu().numpy().view(np.float64)
 
     results = []
     for s in range(B):
@@ -312,25 +230,65 @@ def evaluate_packed(packed, iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), 
                                  id_potential=o['id_potential'][m0:m0 + ng * nt].reshape(ng, nt).copy(),
                                  gt_count=o['gt_count'][g0:g0 + ng].copy(), tr_count=o['tr_count'][t0:t0 + nt].copy())
         results.append(res)
-    if timing:
-        t_end = time.perf_counter()
-        return results, dict(stages_ms={name: events[i].elapsed_time(events[i + 1]) for i, (name, _) in enumerate(stages)},
-                             host_prepare_s=t_prep - t_start, device_and_copies_s=t_back - t_prep,
-                             host_finish_s=t_end - t_back, total_s=t_end - t_start)
-    return results
+    return (results, call.timing_dict()) if timing else results
 
 
-KITTI_STATUS_KINDS = ((1, 0, 'a non-finite box'), (8, 3, 'more rows of one class in one frame than a launch holds'),
-                      (32, 5, 'a workspace slot that is too small'))
+KITTI_STATUS_KINDS = ((1, 'a non-finite box'), (8, 'more rows of one class in one frame than a launch holds'),
+                      (32, 'a workspace slot that is too small'))
 _KITTI_LDS_CELLS = 64 * 64      # frames with more cells than this (rows of all classes) get a workspace slot (section 16)
 _KITTI_MAX_DISTRACTORS = 4
 
 
-def _sorted_by_frame(rows, width):
-    rows = np.asarray(rows, dtype=np.float64).reshape(-1, width)
-    frames = rows[:, 0].astype(np.int64)
+def _sorted_by_frame(rows, frames):
+    """(rows, frames, order) in a stable sort by the integer frame numbers `frames`."""
     order = np.argsort(frames, kind='stable')
     return rows[order], frames[order], order
+
+
+def _frame_tables(sorted_seqs, widths, too_many, cells_per_frame=1):
+    """The per-frame tables of the scoring and preprocessing stages (include/stereotrack.h sections 15, 16 and 21).
+    sorted_seqs: per sequence one (rows, frames, order) triple per row kind, sorted by frame (_sorted_by_frame), widths:
+    the kinds' row widths (ground truth and predictions first).  The frames of a sequence are the union of its kinds'
+    frame numbers.  Returns dict(rows: per kind the rows of all sequences, offs: per kind the (F + 1) int32 row offsets
+    of the frames, frame_ws_off: the workspace cells in front of every frame, orders: per sequence the kinds' sort
+    orders, frame_no, frame_seq, totals, max_frame_objects).  too_many(totals, F): the message when a table does not
+    fit 32 bits."""
+    kinds = range(len(widths))
+    parts, offs, totals = [[np.zeros((0, w))] for w in widths], [[[0]] for _ in kinds], [0 for _ in kinds]
+    orders, frame_no, frame_seq = [], [np.zeros(0, np.int64)], [np.zeros(0, np.int32)]
+    for s, srt in enumerate(sorted_seqs):
+        frames = np.unique(np.concatenate([fr for _, fr, _ in srt]))
+        for k, (rows, fr, _) in enumerate(srt):
+            parts[k].append(rows)
+            offs[k].append(totals[k] + np.searchsorted(fr, frames, 'right'))
+            totals[k] += len(rows)
+        orders.append([o for _, _, o in srt])
+        frame_no.append(frames)
+        frame_seq.append(np.full(len(frames), s, np.int32))
+    t = dict(rows=[np.concatenate(p) for p in parts], offs=[np.concatenate(o).astype(np.int32) for o in offs], orders=orders,
+             frame_no=np.concatenate(frame_no), frame_seq=np.concatenate(frame_seq), totals=totals)
+    F = len(t['frame_no'])
+    if max(totals + [F * cells_per_frame]) >= 2 ** 31 - 1:
+        raise ValueError(too_many(totals, F))
+    G, P = np.diff(t['offs'][0]).astype(np.int64), np.diff(t['offs'][1]).astype(np.int64)
+    t['frame_ws_off'] = np.concatenate([[0], np.cumsum(np.where(G * P > _KITTI_LDS_CELLS, G * P, 0))]).astype(np.int64)
+    t['max_frame_objects'] = int(max(G.max(initial=0), P.max(initial=0)))
+    return t
+
+
+def _keep_masks(orders, keeps):
+    """The keep bytes of the packed rows (per kind, rows on the last axis) as boolean arrays over the rows as they were
+    passed: one tuple per sequence, one array per kind of `keeps`."""
+    out, first = [], [0 for _ in keeps]
+    for seq_orders in orders:
+        masks = []
+        for k, (keep, order) in enumerate(zip(keeps, seq_orders)):
+            m = np.zeros(keep.shape[:-1] + (len(order),), bool)
+            m[..., order] = keep[..., first[k]:first[k] + len(order)] != 0
+            first[k] += len(order)
+            masks.append(m)
+        out.append(tuple(masks))
+    return out
 
 
 def kitti_keep_masks(sequences, classes, max_occlusion=2, max_truncation=0, min_height=25, match_thr=0.5, ignore_thr=0.5,
@@ -341,14 +299,7 @@ def kitti_keep_masks(sequences, classes, max_occlusion=2, max_truncation=0, min_
     any order; classes: a list of (class id, distractor ids).  Returns one (gt_keep (C, n), pred_keep (C, m)) pair of
     boolean arrays per sequence, over the rows as they were passed.  videos: the sequences' names for error messages.
     timing: returns (masks, dict) with the stage's device time (HIP events) and the host clock of the call's parts."""
-    t_start = time.perf_counter()
-    if not torch.cuda.is_available():
-        raise RuntimeError('the device backend of the KITTI preprocessing runs on the HIP path only (csrc/mot_eval.hip) '
-                           'and no CUDA (ROCm) device is available; use backend=\'host\'')
-    lib = _lib.load()
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise RuntimeError(f'the device backend of the KITTI preprocessing needs a CUDA (ROCm) device, got {dev}')
+    call = PackedCall('the KITTI preprocessing', 'csrc/mot_eval.hip', device, timing, LAUNCHES)
     sequences = list(sequences)
     videos = list(range(len(sequences))) if videos is None else list(videos)
     table = np.full((len(classes), 1 + _KITTI_MAX_DISTRACTORS), -1, np.int32)
@@ -363,105 +314,40 @@ def kitti_keep_masks(sequences, classes, max_occlusion=2, max_truncation=0, min_
     if C_ == 0 or not sequences:
         return ([], {}) if timing else []
 
-    # ---- host tables: the frames of a sequence are the union of its three row kinds' frame numbers
-    parts, orders, frame_no, frame_seq = ([], [], []), [], [], []
-    offs = ([0], [0], [0])
-    totals = [0, 0, 0]
-    for s, seq in enumerate(sequences):
-        srt = [_sorted_by_frame(rows, w) for rows, w in zip(seq, (9, 8, 5))]
-        frames = np.unique(np.concatenate([fr for _, fr, _ in srt]))
-        for k, (rows, fr, _) in enumerate(srt):
-            parts[k].append(rows)
-            offs[k].append(totals[k] + np.searchsorted(fr, frames, 'right'))
-            totals[k] += len(rows)
-        orders.append([o for _, _, o in srt])
-        frame_no.append(frames)
-        frame_seq.append(np.full(len(frames), s, np.int32))
-    frame_no, frame_seq = np.concatenate(frame_no), np.concatenate(frame_seq)
-    F = len(frame_no)
-    if max(totals + [F * C_]) >= 2 ** 31 - 1:
-        raise ValueError(f'kitti_keep_masks: {totals} rows, {F} frames x {C_} classes: the offset tables are 32-bit')
-    host_in = dict(gt_rows=np.concatenate(parts[0]), pred_rows=np.concatenate(parts[1]), ignore_rows=np.concatenate(parts[2]),
-                   class_table=table)
-    for k, name in enumerate(('frame_gt_off', 'frame_pred_off', 'frame_ignore_off')):
-        host_in[name] = np.concatenate([np.atleast_1d(a) for a in offs[k]]).astype(np.int32)
-    G, P = np.diff(host_in['frame_gt_off']).astype(np.int64), np.diff(host_in['frame_pred_off']).astype(np.int64)
-    host_in['frame_ws_off'] = np.concatenate([[0], np.cumsum(np.where(G * P > _KITTI_LDS_CELLS, G * P, 0))]).astype(np.int64)
-    NG, NP_, NI = totals
-
-    # ---- one upload
-    lin = _Layout()
-    for k, v in host_in.items():
-        lin.add(k, v.shape, v.dtype)
-    hbuf = np.zeros(lin.size, np.uint8)
-    for k, v in host_in.items():
-        lin.view(hbuf, k)[...] = v
-    t_prep = time.perf_counter()
-    dbuf = torch.from_numpy(hbuf).to(dev)
-    lout = _Layout()
-    for name, shape, dt in (('status', (8,), np.int32), ('gt_keep', (C_, NG), np.uint8), ('pred_keep', (C_, NP_), np.uint8)):
-        lout.add(name, shape, dt)
-    obuf = torch.empty(lout.size, dtype=torch.uint8, device=dev)       # the stage zeroes what it does not write
+    seqs = [[np.asarray(r, dtype=np.float64).reshape(-1, w) for r, w in zip(seq, (9, 8, 5))] for seq in sequences]
+    t = _frame_tables(
+        [[_sorted_by_frame(r, r[:, 0].astype(np.int64)) for r in seq] for seq in seqs], (9, 8, 5),
+        lambda totals, F: f'kitti_keep_masks: {totals} rows, {F} frames x {C_} classes: the offset tables are 32-bit', C_)
+    NG, NP_, NI = t['totals']
+    call.upload(dict(zip(('gt_rows', 'pred_rows', 'ignore_rows', 'class_table', 'frame_gt_off', 'frame_pred_off',
+                          'frame_ignore_off', 'frame_ws_off'), t['rows'] + [table] + t['offs'] + [t['frame_ws_off']])))
+    call.outputs((('status', (8,), np.int32), ('gt_keep', (C_, NG), np.uint8), ('pred_keep', (C_, NP_), np.uint8)))
 
     args = _lib.StMotKittiArgs()
     args.struct_size = C.sizeof(_lib.StMotKittiArgs)
-    args.num_frames, args.num_classes, args.num_gt, args.num_pred, args.num_ignore = F, C_, NG, NP_, NI
-    args.max_frame_objects = int(max(G.max(initial=0), P.max(initial=0)))
-    args.num_ws_cells = int(host_in['frame_ws_off'][-1])
+    args.num_frames, args.num_classes, args.num_gt, args.num_pred, args.num_ignore = len(t['frame_no']), C_, NG, NP_, NI
+    args.max_frame_objects = t['max_frame_objects']
+    args.num_ws_cells = int(t['frame_ws_off'][-1])
     args.max_occlusion, args.max_truncation, args.min_height = float(max_occlusion), float(max_truncation), float(min_height)
     args.match_thr, args.ignore_thr = float(match_thr), float(ignore_thr)
-    for k in host_in:
-        setattr(args, k, C.c_void_p(dbuf.data_ptr() + lin.items[k][0]))
-    for k in lout.items:
-        setattr(args, k, C.c_void_p(obuf.data_ptr() + lout.items[k][0]))
-    nbytes = int(lib.st_mot_kitti_workspace_bytes(C.byref(args)))
-    if nbytes == 0:
-        raise _lib.StError('st_mot_kitti_workspace_bytes: invalid sizes')
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    args.ws, args.ws_bytes = C.c_void_p(ws.data_ptr()), nbytes
-    with torch.cuda.device(dev):
-        events = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timing else None
-        if timing:
-            events[0].record()
-        LAUNCHES['st_mot_kitti_preprocess'] += 1
-        check(lib.st_mot_kitti_preprocess(C.byref(args), current_stream()), 'st_mot_kitti_preprocess')
-        if timing:
-            events[1].record()
-    host = obuf.cpu().numpy()          # the one wait and the one copy back
-    t_back = time.perf_counter()
-    status = lout.view(host, 'status')
-    if status[0]:
-        for bit, kind, what in KITTI_STATUS_KINDS:
-            if int(status[0]) & bit:
-                f = F - int(status[1 + kind])
-                msg = f'KITTI preprocessing: {what}: video {videos[int(frame_seq[f])]!r}, frame {int(frame_no[f])}'
-                if bit == 8:
-                    msg += (f' (at most {max_frame_objects()} ground-truth rows of a class and its distractors and '
-                            f'{max_frame_objects()} prediction rows of the class per frame)')
-                raise ValueError(msg) if bit in (1, 8) else _lib.StError(msg)
-        raise _lib.StError(f'KITTI preprocessing failed on the device: status {int(status[0])}')
-    gk, pk = lout.view(host, 'gt_keep'), lout.view(host, 'pred_keep')
-    out, g0, p0 = [], 0, 0
-    for s, seq in enumerate(sequences):
-        og, op_, _ = orders[s]
-        a, b = np.zeros((C_, len(og)), bool), np.zeros((C_, len(op_)), bool)
-        a[:, og] = gk[:, g0:g0 + len(og)] != 0
-        b[:, op_] = pk[:, p0:p0 + len(op_)] != 0
-        g0, p0 = g0 + len(og), p0 + len(op_)
-        out.append((a, b))
-    if timing:
-        t_end = time.perf_counter()
-        return out, dict(stages_ms={'st_mot_kitti_preprocess': events[0].elapsed_time(events[1])},
-                         host_prepare_s=t_prep - t_start, device_and_copies_s=t_back - t_prep,
-                         host_finish_s=t_end - t_back, total_s=t_end - t_start)
-    return out
+    call.bind(args)
+    call.workspace(args, call.workspace_bytes('st_mot_kitti_workspace_bytes', args))
+    with call.stages():
+        call.launch('st_mot_kitti_preprocess', C.byref(args))
+    host = call.fetch()
+    if host['status'][0]:
+        _raise_status('KITTI preprocessing', KITTI_STATUS_KINDS, host['status'], videos, t['frame_seq'], t['frame_no'],
+                      ' (at most {n} ground-truth rows of a class and its distractors and {n} prediction rows of the class '
+                      'per frame)')
+    out = _keep_masks(t['orders'], (host['gt_keep'], host['pred_keep']))
+    return (out, call.timing_dict()) if timing else out
 
 
-CHALLENGE_STATUS_KINDS = ((1, 0, 'a non-finite box'), (8, 3, 'more rows in one frame than a launch holds'),
-                          (32, 5, 'a workspace slot that is too small'))
+CHALLENGE_STATUS_KINDS = ((1, 'a non-finite box'), (8, 'more rows in one frame than a launch holds'),
+                          (32, 'a workspace slot that is too small'))
 FILE_COPY, FILE_TRUNCATE, FILE_ROUND3 = 0, 1, 2          # ST_MOT_FILE_* of include/stereotrack.h section 21
 _FILE_MODES = dict(gt=(FILE_TRUNCATE,) * 8, pred=(FILE_TRUNCATE,) * 2 + (FILE_ROUND3,) * 5)
-_FILE_STATUS_KINDS = ((1, 0, 'a non-finite value'), (2, 1, 'a value of 2^43 or more in a column written with %.3f'))
+_FILE_STATUS_KINDS = ((1, 'a non-finite value'), (2, 'a value of 2^43 or more in a column written with %.3f'))
 
 
 def file_round(rows_dev, modes, out_dev, status_dev):
@@ -480,23 +366,16 @@ def _challenge_device(gts, preds, benchmark, device, videos, timing):
     """The device flow shared by motchallenge_keep_masks and evaluate_motchallenge: one upload, the two roundings, the
     preprocessing, one wait and one copy back of the status words and the keep bytes."""
     from . import metrics as M
-    t_start = time.perf_counter()
     distractors = M.motchallenge_distractors(benchmark)
-    if not torch.cuda.is_available():
-        raise RuntimeError('the device backend of the MOTChallenge protocol runs on the HIP path only (csrc/mot_eval.hip) '
-                           'and no CUDA (ROCm) device is available; use backend=\'host\'')
-    lib = _lib.load()
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise RuntimeError(f'the device backend of the MOTChallenge protocol needs a CUDA (ROCm) device, got {dev}')
+    call = PackedCall('the MOTChallenge protocol', 'csrc/mot_eval.hip', device, timing, LAUNCHES)
+    dev = call.dev
     gts, preds = list(gts), list(preds)
     if len(gts) != len(preds):
         raise ValueError(f'MOTChallenge protocol: {len(gts)} ground-truth sets against {len(preds)} prediction sets')
     videos = list(range(len(gts))) if videos is None else list(videos)
 
     # ---- host tables, from the truncated frame column only; the class check needs the class column's integer part
-    parts, orders, frames_of, frame_no, frame_seq = ([], []), [], [], [], []
-    offs, totals = ([0], [0]), [0, 0]
+    srt = []
     for s, (g, p) in enumerate(zip(gts, preds)):
         g, p = M.motchallenge_gt8(g), M.motchallenge_pred7(p)
         M._require_finite(g, 'ground-truth', videos[s])
@@ -506,117 +385,53 @@ def _challenge_device(gts, preds, benchmark, device, videos, timing):
         if len(bad):
             raise ValueError(f'MOTChallenge preprocessing: video {videos[s]!r}: ground-truth row {int(bad[0])} has class '
                              f'{cls[bad[0]]:g}, outside 1..{M.MOTCHALLENGE_NUM_CLASSES}')
-        srt = []
-        for rows in (g, p):
-            fr = np.trunc(rows[:, 0]).astype(np.int64)
-            order = np.argsort(fr, kind='stable')
-            srt.append((rows[order], fr[order], order))
-        frames = np.union1d(srt[0][1], srt[1][1])
-        for k, (rows, fr, _) in enumerate(srt):
-            parts[k].append(rows)
-            offs[k].append(totals[k] + np.searchsorted(fr, frames, 'right'))
-            totals[k] += len(rows)
-        orders.append((srt[0][2], srt[1][2]))
-        frames_of.append((srt[0][1], srt[1][1]))
-        frame_no.append(frames)
-        frame_seq.append(np.full(len(frames), s, np.int32))
-    frame_no = np.concatenate(frame_no + [np.zeros(0, np.int64)])
-    frame_seq = np.concatenate(frame_seq + [np.zeros(0, np.int32)])
-    F, (NG, NP_) = len(frame_no), totals
-    if max(NG, NP_, F) >= 2 ** 31 - 1:
-        raise ValueError(f'MOTChallenge protocol: {NG} ground-truth rows, {NP_} prediction rows, {F} frames: the offset tables '
-                         f'are 32-bit')
-    host_in = dict(gt_rows=np.concatenate(parts[0] + [np.zeros((0, 8))]), pred_rows=np.concatenate(parts[1] + [np.zeros((0, 7))]))
-    for k, name in enumerate(('frame_gt_off', 'frame_pred_off')):
-        host_in[name] = np.concatenate([np.atleast_1d(a) for a in offs[k]]).astype(np.int32)
-    G, P = np.diff(host_in['frame_gt_off']).astype(np.int64), np.diff(host_in['frame_pred_off']).astype(np.int64)
-    host_in['frame_ws_off'] = np.concatenate([[0], np.cumsum(np.where(G * P > _KITTI_LDS_CELLS, G * P, 0))]).astype(np.int64)
-
-    # ---- one upload
-    lin = _Layout()
-    for k, v in host_in.items():
-        lin.add(k, v.shape, v.dtype)
-    hbuf = np.zeros(lin.size, np.uint8)
-    for k, v in host_in.items():
-        lin.view(hbuf, k)[...] = v
-    t_prep = time.perf_counter()
-    dbuf = torch.from_numpy(hbuf).to(dev)
-    lout = _Layout()
-    for name, shape, dt in (('status_gt', (8,), np.int32), ('status_pred', (8,), np.int32), ('status', (8,), np.int32),
-                            ('gt_keep', (NG,), np.uint8), ('pred_keep', (NP_,), np.uint8)):
-        lout.add(name, shape, dt)
-    obuf = torch.empty(lout.size, dtype=torch.uint8, device=dev)       # the stages zero what they do not write
-    dview = lambda name: _device_view(lin, dbuf, name)
-    oview = lambda name: _device_view(lout, obuf, name)
+        srt.append([_sorted_by_frame(rows, np.trunc(rows[:, 0]).astype(np.int64)) for rows in (g, p)])
+    t = _frame_tables(srt, (8, 7), lambda totals, F: f'MOTChallenge protocol: {totals[0]} ground-truth rows, {totals[1]} '
+                                                     f'prediction rows, {F} frames: the offset tables are 32-bit')
+    NG, NP_ = t['totals']
+    call.upload(dict(zip(('gt_rows', 'pred_rows', 'frame_gt_off', 'frame_pred_off', 'frame_ws_off'),
+                         t['rows'] + t['offs'] + [t['frame_ws_off']])))
+    call.outputs((('status_gt', (8,), np.int32), ('status_pred', (8,), np.int32), ('status', (8,), np.int32),
+                  ('gt_keep', (NG,), np.uint8), ('pred_keep', (NP_,), np.uint8)))
     gt_file = torch.empty((NG, 8), dtype=torch.float64, device=dev)    # the rows a reader of the files gets
     pred_file = torch.empty((NP_, 7), dtype=torch.float64, device=dev)
 
     args = _lib.StMotChallengeArgs()
     args.struct_size = C.sizeof(_lib.StMotChallengeArgs)
-    args.num_frames, args.num_gt, args.num_pred = F, NG, NP_
-    args.max_frame_objects = int(max(G.max(initial=0), P.max(initial=0)))
+    args.num_frames, args.num_gt, args.num_pred = len(t['frame_no']), NG, NP_
+    args.max_frame_objects = t['max_frame_objects']
     args.do_preproc = int(benchmark != 'MOT15')
     args.num_distractors = len(distractors)
     for k, d in enumerate(distractors):
         args.distractors[k] = int(d)
-    args.num_ws_cells = int(host_in['frame_ws_off'][-1])
+    args.num_ws_cells = int(t['frame_ws_off'][-1])
+    call.bind(args, ('frame_gt_off', 'frame_pred_off', 'frame_ws_off'), ('gt_keep', 'pred_keep', 'status'))
     args.gt_rows, args.pred_rows = C.c_void_p(gt_file.data_ptr()), C.c_void_p(pred_file.data_ptr())
-    for k in ('frame_gt_off', 'frame_pred_off', 'frame_ws_off'):
-        setattr(args, k, C.c_void_p(dbuf.data_ptr() + lin.items[k][0]))
-    for k in ('gt_keep', 'pred_keep', 'status'):
-        setattr(args, k, C.c_void_p(obuf.data_ptr() + lout.items[k][0]))
-    nbytes = int(lib.st_mot_challenge_workspace_bytes(C.byref(args)))
-    if nbytes == 0:
-        raise _lib.StError('st_mot_challenge_workspace_bytes: invalid sizes')
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    args.ws, args.ws_bytes = C.c_void_p(ws.data_ptr()), nbytes
-    with torch.cuda.device(dev):
-        events = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing else None
-        if timing:
-            events[0].record()
-        file_round(dview('gt_rows'), _FILE_MODES['gt'], gt_file, oview('status_gt'))
-        file_round(dview('pred_rows'), _FILE_MODES['pred'], pred_file, oview('status_pred'))
-        if timing:
-            events[1].record()
-        LAUNCHES['st_mot_challenge_preprocess'] += 1
-        check(lib.st_mot_challenge_preprocess(C.byref(args), current_stream()), 'st_mot_challenge_preprocess')
-        if timing:
-            events[2].record()
-    host = obuf.cpu().numpy()          # the one wait and the one copy back
-    t_back = time.perf_counter()
+    call.workspace(args, call.workspace_bytes('st_mot_challenge_workspace_bytes', args))
+    with call.stages():
+        call.begin('st_mot_file_round')
+        file_round(call.device_in('gt_rows'), _FILE_MODES['gt'], gt_file, call.device_out('status_gt'))
+        file_round(call.device_in('pred_rows'), _FILE_MODES['pred'], pred_file, call.device_out('status_pred'))
+        call.launch('st_mot_challenge_preprocess', C.byref(args))
+    host = call.fetch()
 
     def row_of(kind, packed_row):      # (video, index among the rows as they were passed) of a packed row
-        bounds = np.cumsum([0] + [len(o[kind]) for o in orders])
+        bounds = np.cumsum([0] + [len(o[kind]) for o in t['orders']])
         s = int(np.searchsorted(bounds, packed_row, 'right')) - 1
-        return videos[s], int(orders[s][kind][packed_row - bounds[s]])
+        return videos[s], int(t['orders'][s][kind][packed_row - bounds[s]])
     for kind, (name, total) in enumerate((('status_gt', NG), ('status_pred', NP_))):
-        st = lout.view(host, name)
-        for bit, k, what in _FILE_STATUS_KINDS:
+        st = host[name]
+        for bit, what in _FILE_STATUS_KINDS:
             if int(st[0]) & bit:
-                video, row = row_of(kind, total - int(st[1 + k]))
+                video, row = row_of(kind, total - int(st[bit.bit_length()]))
                 raise ValueError(f'MOTChallenge files: {what}: video {video!r}, {("ground-truth", "prediction")[kind]} row {row}')
         if st[0]:
             raise _lib.StError(f'st_mot_file_round failed on the device: status {int(st[0])}')
-    status = lout.view(host, 'status')
-    if status[0]:
-        for bit, kind, what in CHALLENGE_STATUS_KINDS:
-            if int(status[0]) & bit:
-                f = F - int(status[1 + kind])
-                msg = f'MOTChallenge preprocessing: {what}: video {videos[int(frame_seq[f])]!r}, frame {int(frame_no[f])}'
-                if bit == 8:
-                    msg += f' (at most {max_frame_objects()} ground-truth and {max_frame_objects()} prediction rows per frame)'
-                raise ValueError(msg) if bit in (1, 8) else _lib.StError(msg)
-        raise _lib.StError(f'MOTChallenge preprocessing failed on the device: status {int(status[0])}')
-    out = dict(gt_file=gt_file, pred_file=pred_file, gt_keep=lout.view(host, 'gt_keep'), pred_keep=lout.view(host, 'pred_keep'),
-               orders=orders, frames_of=frames_of, sorted_rows=parts, videos=videos, device=dev)
-    if timing:
-        out['timing'] = dict(events=events, host_prepare_s=t_prep - t_start, device_and_copies_s=t_back - t_prep, t_back=t_back)
-    return out
-
-
-def _challenge_stage_ms(r):
-    ev = r['timing']['events']
-    return {'st_mot_file_round': ev[0].elapsed_time(ev[1]), 'st_mot_challenge_preprocess': ev[1].elapsed_time(ev[2])}
+    if host['status'][0]:
+        _raise_status('MOTChallenge preprocessing', CHALLENGE_STATUS_KINDS, host['status'], videos, t['frame_seq'],
+                      t['frame_no'], ' (at most {n} ground-truth and {n} prediction rows per frame)')
+    return dict(gt_file=gt_file, pred_file=pred_file, gt_keep=host['gt_keep'], pred_keep=host['pred_keep'],
+                orders=t['orders'], sorted=srt, videos=videos, call=call)
 
 
 def motchallenge_keep_masks(gts, preds, benchmark='MOT17', device=None, videos=None, timing=False):
@@ -629,19 +444,8 @@ def motchallenge_keep_masks(gts, preds, benchmark='MOT17', device=None, videos=N
     boolean arrays per sequence, over the rows as they were passed.  videos: the names for error messages.
     timing: returns (masks, dict) with the stages' device time (HIP events) and the host clock of the call's parts."""
     r = _challenge_device(gts, preds, benchmark, device, videos, timing)
-    out, g0, p0 = [], 0, 0
-    for og, op_ in r['orders']:
-        a, b = np.zeros(len(og), bool), np.zeros(len(op_), bool)
-        a[og] = r['gt_keep'][g0:g0 + len(og)] != 0
-        b[op_] = r['pred_keep'][p0:p0 + len(op_)] != 0
-        g0, p0 = g0 + len(og), p0 + len(op_)
-        out.append((a, b))
-    if timing:
-        t = r['timing']
-        t_end = time.perf_counter()
-        return out, dict(stages_ms=_challenge_stage_ms(r), host_prepare_s=t['host_prepare_s'],
-                         device_and_copies_s=t['device_and_copies_s'], host_finish_s=t_end - t['t_back'])
-    return out
+    out = _keep_masks(r['orders'], (r['gt_keep'], r['pred_keep']))
+    return (out, r['call'].timing_dict()) if timing else out
 
 
 def evaluate_motchallenge(gts, preds, benchmark='MOT17', iou_thr=0.5, metrics=('HOTA', 'CLEAR', 'Identity'), device=None,
@@ -657,20 +461,21 @@ def evaluate_motchallenge(gts, preds, benchmark='MOT17', iou_thr=0.5, metrics=('
     for kind, keep in enumerate((r['gt_keep'], r['pred_keep'])):
         kept.append(np.nonzero(keep)[0])
         r0 = 0
-        for s, rows in enumerate(r['sorted_rows'][kind]):
+        for s, seq in enumerate(r['sorted']):
+            rows, frames, _ = seq[kind]
             m = keep[r0:r0 + len(rows)] != 0
             head = np.zeros((int(m.sum()), 6))
-            head[:, 0], head[:, 1] = r['frames_of'][s][kind][m], np.trunc(rows[m, 1])
+            head[:, 0], head[:, 1] = frames[m], np.trunc(rows[m, 1])
             by_video[kind][keys[s]] = head
             r0 += len(rows)
     packed = pack_sequences(*by_video)
-    dev = r['device']
+    dev = r['call'].dev
     boxes = [src[torch.from_numpy(idx).to(dev)][:, 2:6].contiguous() for src, idx in zip((r['gt_file'], r['pred_file']), kept)]
     res = evaluate_packed(packed, iou_thr, metrics, dev, timing=timing, device_boxes=boxes)
     if timing:
         res, t = res
-        t['challenge'] = dict(stages_ms=_challenge_stage_ms(r), host_prepare_s=r['timing']['host_prepare_s'],
-                              device_and_copies_s=r['timing']['device_and_copies_s'])
+        challenge = r['call'].timing_dict()
+        t['challenge'] = {k: challenge[k] for k in ('stages_ms', 'host_prepare_s', 'device_and_copies_s')}
         return res, t
     return res
 

@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._packed import PackedCall
 from .metrics import _check_backend
 from .registry import TASK_UTILS
 
@@ -239,20 +240,14 @@ class InterpolateTracklets:
         return out
 
     def _forward_many_device(self, row_arrays, device, budget, timing):
-        t_start = time.perf_counter()
-        if not torch.cuda.is_available():
-            raise RuntimeError('the device backend of InterpolateTracklets runs on the HIP path only '
-                               '(csrc/tracklet_post.hip) and no CUDA (ROCm) device is available; use backend=\'host\'')
-        lib = _lib.load()
-        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        if dev.type != 'cuda':
-            raise RuntimeError(f'the device backend of InterpolateTracklets needs a CUDA (ROCm) device, got {dev}')
+        call = PackedCall('InterpolateTracklets', 'csrc/tracklet_post.hip', device, timing, LAUNCHES)
+        lib, dev = call.lib, call.dev
         budget = WORKSPACE_BUDGET_BYTES if budget is None else int(budget)
         p = self._plan(row_arrays)
         B, T, R, M = len(row_arrays), p['T'], p['R'], p['M']
         if T == 0:
             out = [np.zeros((0, 7)) for _ in range(B)]
-            return (out, dict(stages_ms={}, host_prepare_s=time.perf_counter() - t_start)) if timing else out
+            return (out, dict(stages_ms={}, host_prepare_s=time.perf_counter() - call.t_start)) if timing else out
         n_sorted = p['n_out'][p['trk_order']]
         ranges = []
         if self.use_gsi:
@@ -263,73 +258,38 @@ class InterpolateTracklets:
             cus = torch.cuda.get_device_properties(dev).multi_processor_count
             ranges = self._launch_ranges(n_sorted, lib, cus, budget)
 
-        from .mot_eval import _Layout
-        host_in = {k: p[k] for k in ('rows', 'row_out_off', 'row_gap', 'trk_out_off', 'trk_order', 'trk_len_scale')}
-        lin = _Layout()
-        for k, v in host_in.items():
-            lin.add(k, v.shape, v.dtype)
-        hbuf = np.zeros(lin.size, np.uint8)
-        for k, v in host_in.items():
-            lin.view(hbuf, k)[...] = v
-        lout = _Layout()
-        lout.add('status', (T,), np.int32)
-        lout.add('out_rows', (M, 7), np.float64)
-
         args = _lib.StTrackletArgs()
         args.struct_size = C.sizeof(_lib.StTrackletArgs)
         args.num_rows, args.num_out_rows, args.num_tracks = R, M, T
         launches, ws_bytes = [], 256
         for first, count, groups in ranges:
             args.num_groups, args.max_rows = groups, int(n_sorted[first])
-            need = int(lib.st_tracklet_gsi_workspace_bytes(C.byref(args)))
-            if need == 0:
-                raise _lib.StError('st_tracklet_gsi_workspace_bytes: invalid sizes')
             launches.append((first, count, groups, int(n_sorted[first])))
-            ws_bytes = max(ws_bytes, need)
-        t_prep = time.perf_counter()
+            ws_bytes = max(ws_bytes, call.workspace_bytes('st_tracklet_gsi_workspace_bytes', args))
 
-        dbuf = torch.from_numpy(hbuf).to(dev)                                # the one upload
-        obuf = torch.empty(lout.size, dtype=torch.uint8, device=dev)        # st_tracklet_interpolate zeroes the status
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        call.upload({k: p[k] for k in ('rows', 'row_out_off', 'row_gap', 'trk_out_off', 'trk_order', 'trk_len_scale')})
+        call.outputs((('status', (T,), np.int32), ('out_rows', (M, 7), np.float64)))    # the status: zeroed by the first stage
+        call.workspace(args, ws_bytes)
         ticks = torch.zeros((max([g for _, _, g, _ in launches] + [1]), 4), dtype=torch.int64, device=dev) if timing else None
         args.phase_ticks = C.c_void_p(ticks.data_ptr()) if timing else None
-        for k in host_in:
-            setattr(args, k, C.c_void_p(dbuf.data_ptr() + lin.items[k][0]))
-        for k in lout.items:
-            setattr(args, k, C.c_void_p(obuf.data_ptr() + lout.items[k][0]))
-        args.ws, args.ws_bytes = C.c_void_p(ws.data_ptr()), ws_bytes
-        with torch.cuda.device(dev):
-            stream = _lib.current_stream()
-            events = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing else None
-            if timing:
-                events[0].record()
+        call.bind(args)
+        with call.stages():
             args.first = args.count = 0
             args.num_groups = args.max_rows = 1
-            LAUNCHES['st_tracklet_interpolate'] += 1
-            _lib.check(lib.st_tracklet_interpolate(C.byref(args), stream), 'st_tracklet_interpolate')
-            if timing:
-                events[1].record()
+            call.launch('st_tracklet_interpolate', C.byref(args))
+            call.begin('st_tracklet_gsi')
             for first, count, groups, nmax in launches:
                 args.first, args.count, args.num_groups, args.max_rows = first, count, groups, nmax
-                LAUNCHES['st_tracklet_gsi'] += 1
-                _lib.check(lib.st_tracklet_gsi(C.byref(args), stream), 'st_tracklet_gsi')
-            if timing:
-                events[2].record()
-        host = obuf.cpu().numpy()              # the one wait and the one copy back
-        t_back = time.perf_counter()
-        status = lout.view(host, 'status')
-        _raise_status(status, p)
-        rows = lout.view(host, 'out_rows')
+                call.launch('st_tracklet_gsi', C.byref(args))
+        host = call.fetch()
+        _raise_status(host['status'], p)
+        rows = host['out_rows']
         set_off = np.searchsorted(np.repeat(p['trk_set'], p['n_out']), np.arange(B + 1))
         out = [_finish(rows[set_off[s]:set_off[s + 1]]) for s in range(B)]
         if timing:
-            t_end = time.perf_counter()
+            tm = call.timing_dict(gsi_launches=len(launches), tracks=T, rows_in=R, rows_out=M)
             phase = ticks.sum(0).cpu().numpy().astype(np.float64)      # after the timed part: a second, small copy
-            return out, dict(gsi_phase_share=dict(zip(('build_k', 'factorisation', 'solves', 'product'),
-                                                      (phase / max(1.0, phase.sum())).tolist())),
-                             stages_ms={'st_tracklet_interpolate': events[0].elapsed_time(events[1]),
-                                        'st_tracklet_gsi': events[1].elapsed_time(events[2])},
-                             gsi_launches=len(launches), tracks=T, rows_in=R, rows_out=M,
-                             host_prepare_s=t_prep - t_start, device_and_copies_s=t_back - t_prep,
-                             host_finish_s=t_end - t_back, total_s=t_end - t_start)
+            tm['gsi_phase_share'] = dict(zip(('build_k', 'factorisation', 'solves', 'product'),
+                                             (phase / max(1.0, phase.sum())).tolist()))
+            return out, tm
         return out
