@@ -88,6 +88,80 @@ int st_jpeg_reconstruct(const int16_t* coef_dev, const uint16_t* quant_dev, int 
                         size_t work_bytes, uint8_t* out_dev, ptrdiff_t image_stride, ptrdiff_t plane_stride,
                         ptrdiff_t row_stride, int rgb_order, st_stream_t stream);
 
+/* ---- entropy decode on the device (opt-in; DESIGN.md 25 "Entropy decode on the device") -----------------------------
+ *
+ * st_jpeg_entropy_decode above is the specification: for every byte string the device path gives the same coefficients,
+ * the same tables and the same accept / refuse verdict.  The host only parses the headers (st_jpeg_entropy_prepare,
+ * O(header)) and copies the scan bytes; markers inside the scan are found on the device.
+ *
+ * One call takes ONE blob, the same bytes in page-locked host memory and (after the caller's H2D copy, enqueued on the
+ * same stream in front of the call) in device memory:
+ *   [0, N * sizeof(StJpegEntropyDesc))   the descriptors, image n at n * sizeof(StJpegEntropyDesc)
+ *   desc[n].blob_offset ...              the file's bytes from scan_offset to its end (scan_bytes of them), at a
+ *                                        16-byte aligned offset the caller chooses and writes into the descriptor */
+typedef struct StJpegHuffLut {
+  uint16_t fast[512];  /* 9-bit prefix -> (length << 8) | symbol, 0 = longer than 9 bits */
+  int32_t maxcode[18]; /* largest code of each length, -1 = none; [17] = INT32_MAX */
+  int32_t valptr[17], mincode[17];
+  uint8_t vals[256];
+} StJpegHuffLut;
+
+typedef struct StJpegEntropyDesc {
+  int struct_size;
+  int components, sampling, restart_interval; /* as in StJpegInfo */
+  int mcus_x, mcus_y;
+  int dc_slot[3], ac_slot[3]; /* component -> index into dc[] / ac[] */
+  unsigned scan_offset;       /* first entropy-coded byte in the file */
+  unsigned scan_bytes;        /* file bytes from there to the end of the file (trailing markers included) */
+  unsigned blob_offset;       /* where the caller put those bytes in the blob; st_jpeg_entropy_prepare writes 0 */
+  int reserved;
+  uint16_t quant[3][64]; /* natural order, per component (absent components: zero) */
+  StJpegHuffLut dc[3], ac[3];
+} StJpegEntropyDesc;
+
+typedef struct StJpegEntropyTuning {
+  int struct_size;
+  int subseq_bytes; /* raw scan bytes per thread, 8 .. 512; 0 = default (32) */
+  int tile;         /* subsequences per tile, 1 .. 256; 0 = default (256); subseq_bytes * tile <= 32768 */
+} StJpegEntropyTuning;
+
+typedef struct StJpegEntropyStats { /* one per image, at the start of the work memory */
+  int tiles, subsequences;
+  int max_passes; /* most decode passes any tile needed before its exits settled (>= 1; 0 for an empty scan) */
+  int sum_passes; /* over all tiles */
+} StJpegEntropyStats;
+
+/* Header parse of one file into *desc (desc->struct_size set by the caller).  Refuses exactly what st_jpeg_info and the
+ * table checks of st_jpeg_entropy_decode refuse, with the same status and message (and files of 256 MiB and more: raw
+ * bit positions are 32-bit); never reads the scan bytes. */
+int st_jpeg_entropy_prepare(const uint8_t* data, size_t nbytes, StJpegEntropyDesc* desc);
+
+/* Device work memory of a call over N images: N StJpegEntropyStats, rounded up to 256 bytes; 0 on a bad argument. */
+size_t st_jpeg_entropy_work_bytes(const StJpegInfo* info, int N);
+
+/* Entropy decode of N images of ONE geometry and sampling class on `stream` (two launches, no wait, no D2H copy):
+ *   blob_host    the blob in host memory: only its descriptors are read, to refuse on the host, before any launch, a
+ *                descriptor that does not match *info or whose scan does not lie inside [N * sizeof(desc), blob_bytes)
+ *   blob_dev     the same blob on the device, 16-byte aligned
+ *   coef_dev     N x coef_count int16, the layout of st_jpeg_entropy_decode; every element of an accepted image is
+ *                written, a refused image's are unspecified (nothing outside its own extent is written)
+ *   quant_dev    N x 3 x 64 uint16
+ *   status_dev   N int32: 0 = accepted, non-zero (ST_JPEG_E_* bits) exactly when st_jpeg_entropy_decode refuses the
+ *                file's entropy data
+ *   work_dev     >= st_jpeg_entropy_work_bytes(info, N), 16-byte aligned; arbitrary bits before, the stats after
+ *   tuning       NULL = defaults
+ * Reads nothing outside the blob, writes nothing outside coef / quant / status / work. */
+#define ST_JPEG_E_CODE 1      /* a code not in the table */
+#define ST_JPEG_E_RUN 2       /* a run past coefficient 63, a ZRL past 64 */
+#define ST_JPEG_E_DC 4        /* a DC predictor outside int16 */
+#define ST_JPEG_E_SHORT 8     /* the data (or a restart interval) ends before its MCUs do */
+#define ST_JPEG_E_LEFTOVER 16 /* 8 or more bits before an expected RSTn */
+#define ST_JPEG_E_MARKER 32   /* the expected RSTn is missing or misnumbered */
+int st_jpeg_entropy_decode_dev(const uint8_t* blob_host, const uint8_t* blob_dev, size_t blob_bytes, int N,
+                               const StJpegInfo* info, const StJpegEntropyTuning* tuning, int16_t* coef_dev,
+                               uint16_t* quant_dev, int32_t* status_dev, void* work_dev, size_t work_bytes,
+                               st_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -402,6 +402,51 @@ extern "C" int st_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, int16_
   return ST_OK;
 }
 
+// The host half of the device entropy decode (jpeg_entropy.hip): the header parse and the table checks of
+// st_jpeg_entropy_decode, written out as one fixed-size descriptor.  The entropy-coded bytes are not looked at.
+extern "C" int st_jpeg_entropy_prepare(const uint8_t* data, size_t nbytes, StJpegEntropyDesc* desc) {
+  ST_REQUIRE(data && desc, "st_jpeg_entropy_prepare: null argument");
+  ST_REQUIRE(desc->struct_size == (int)sizeof(StJpegEntropyDesc),
+             "st_jpeg_entropy_prepare: StJpegEntropyDesc.struct_size %d, this library has %d", desc->struct_size,
+             (int)sizeof(StJpegEntropyDesc));
+  Header H;
+  H.info.struct_size = (int)sizeof(StJpegInfo);
+  ST_CHECK(parse_header(data, nbytes, H));
+  const StJpegInfo& I = H.info;
+  ST_REQUIRE(nbytes < ((size_t)1 << 28), "st_jpeg_entropy_prepare: files of 256 MiB and more are not decoded on the device");
+  StJpegEntropyDesc& D = *desc;
+  std::memset(&D, 0, sizeof(D));
+  D.struct_size = (int)sizeof(D);
+  D.components = I.components;
+  D.sampling = I.sampling;
+  D.restart_interval = I.restart_interval;
+  D.mcus_x = I.mcus_x;
+  D.mcus_y = I.mcus_y;
+  D.scan_offset = (unsigned)H.scan_pos;
+  D.scan_bytes = (unsigned)(nbytes - H.scan_pos);
+  auto fill = [](StJpegHuffLut& L, const Huff& h) {
+    std::memcpy(L.fast, h.fast, sizeof(L.fast));
+    std::memcpy(L.maxcode, h.maxcode, sizeof(L.maxcode));
+    std::memcpy(L.valptr + 1, h.valptr + 1, 16 * sizeof(int32_t));
+    std::memcpy(L.mincode + 1, h.mincode + 1, 16 * sizeof(int32_t));
+    L.maxcode[0] = -1;
+    std::memcpy(L.vals, h.vals, sizeof(L.vals));
+  };
+  for (int c = 0; c < I.components; ++c) {
+    ST_REQUIRE(H.quant_defined[H.tq[c]], "JPEG: component %d uses quantisation table %d, which the file does not define", c, H.tq[c]);
+    ST_REQUIRE(H.dc[H.td[c]].defined && H.ac[H.ta[c]].defined, "JPEG: component %d uses a Huffman table the file does not define", c);
+    std::memcpy(D.quant[c], H.quant[H.tq[c]], 64 * sizeof(uint16_t));
+    D.dc_slot[c] = D.ac_slot[c] = c;
+    for (int e = c - 1; e >= 0; --e) {                  // components that name one table share its slot
+      if (H.td[e] == H.td[c]) D.dc_slot[c] = D.dc_slot[e];
+      if (H.ta[e] == H.ta[c]) D.ac_slot[c] = D.ac_slot[e];
+    }
+    if (D.dc_slot[c] == c) fill(D.dc[c], H.dc[H.td[c]]);
+    if (D.ac_slot[c] == c) fill(D.ac[c], H.ac[H.ta[c]]);
+  }
+  return ST_OK;
+}
+
 extern "C" int st_jpeg_reconstruct_host(const int16_t* coef, const uint16_t* quant, const StJpegInfo* info, uint8_t* out,
                                         ptrdiff_t plane_stride, ptrdiff_t row_stride, ptrdiff_t pixel_stride, int rgb_order) {
   namespace J = st::jpeg;

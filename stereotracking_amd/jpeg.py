@@ -9,7 +9,9 @@ MJPEG.  A decoder splits along this package's host / device line:
   JpegDecoder             entropy decode on a few host threads into page-locked memory, ONE H2D copy of the quantised
                           coefficients, then dequantisation + inverse DCT + chroma upsampling + YCbCr -> BGR in HIP
                           (csrc/jpeg_decode.hip): uint8 planar (N,3,h,w) frames on the device, what RawFrames and the raw
-                          stem kernels take
+                          stem kernels take.  entropy='device' (opt-in): the host only parses headers and copies the raw scan
+                          bytes; the Huffman decode runs in HIP too (csrc/jpeg_entropy.hip), equal to the host routine in
+                          coefficients, tables and accept / refuse verdict
   write_jpeg              a small numpy baseline ENCODER (Annex K tables, IJG quality scaling), the counterpart of
                           write_png: tests and tools make JPEGs of any geometry without an imaging library
 
@@ -38,6 +40,25 @@ class StJpegInfo(C.Structure):
                 ('coef_bytes', C.c_size_t), ('work_bytes', C.c_size_t)]
 
 
+class StJpegHuffLut(C.Structure):
+    _fields_ = [('fast', C.c_uint16 * 512), ('maxcode', C.c_int32 * 18), ('valptr', C.c_int32 * 17),
+                ('mincode', C.c_int32 * 17), ('vals', C.c_uint8 * 256)]
+
+
+class StJpegEntropyDesc(C.Structure):
+    _fields_ = [('struct_size', C.c_int), ('components', C.c_int), ('sampling', C.c_int), ('restart_interval', C.c_int),
+                ('mcus_x', C.c_int), ('mcus_y', C.c_int), ('dc_slot', C.c_int * 3), ('ac_slot', C.c_int * 3),
+                ('scan_offset', C.c_uint), ('scan_bytes', C.c_uint), ('blob_offset', C.c_uint), ('reserved', C.c_int),
+                ('quant', C.c_uint16 * 64 * 3), ('dc', StJpegHuffLut * 3), ('ac', StJpegHuffLut * 3)]
+
+
+class StJpegEntropyTuning(C.Structure):
+    _fields_ = [('struct_size', C.c_int), ('subseq_bytes', C.c_int), ('tile', C.c_int)]
+
+
+DESC_BYTES = C.sizeof(StJpegEntropyDesc)
+assert DESC_BYTES % 16 == 0
+
 _PROTOS = {
     'st_jpeg_info': (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(StJpegInfo)]),
     'st_jpeg_entropy_decode': (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -46,6 +67,11 @@ _PROTOS = {
     'st_jpeg_work_bytes': (C.c_size_t, [C.POINTER(StJpegInfo), C.c_int]),
     'st_jpeg_reconstruct': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(StJpegInfo), C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_ssize_t, C.c_ssize_t, C.c_ssize_t, C.c_int, C.c_void_p]),
+    'st_jpeg_entropy_prepare': (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p]),
+    'st_jpeg_entropy_work_bytes': (C.c_size_t, [C.POINTER(StJpegInfo), C.c_int]),
+    'st_jpeg_entropy_decode_dev': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(StJpegInfo),
+                                             C.POINTER(StJpegEntropyTuning), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_size_t, C.c_void_p]),
 }
 _bound = None
 _bind_lock = threading.Lock()
@@ -116,6 +142,104 @@ def entropy_decode(data, coef=None, quant=None):
     assert quant.dtype == np.uint16 and quant.size == 192 and quant.flags.c_contiguous
     _check(_api().st_jpeg_entropy_decode(data, len(data), coef.ctypes.data, quant.ctypes.data), 'st_jpeg_entropy_decode')
     return info, coef, quant
+
+
+def entropy_prepare(data, into=None, index=0):
+    """The header parse of the device entropy decode (st_jpeg_entropy_prepare, O(header)) -> StJpegEntropyDesc with
+    blob_offset 0; `into`: a writable uint8 numpy array that holds descriptors, the struct is then a view of slot `index`."""
+    d = StJpegEntropyDesc() if into is None else StJpegEntropyDesc.from_buffer(into, index * DESC_BYTES)
+    d.struct_size = DESC_BYTES
+    _check(_api().st_jpeg_entropy_prepare(data, len(data), C.addressof(d)), 'st_jpeg_entropy_prepare')
+    return d
+
+
+def blob_capacity(datas):
+    """Bytes that build_blob needs at most for these files."""
+    return len(datas) * DESC_BYTES + sum((len(d) + 15) // 16 * 16 for d in datas)
+
+
+def build_blob(datas, host=None, pool=None):
+    """The ONE blob of a device entropy decode: N descriptors, then every file's bytes from its scan on, each at a
+    16-byte aligned offset.  host: a uint8 numpy array of at least blob_capacity(datas) (page-locked in JpegDecoder).
+    pool: an executor for the per-image work.  -> (host, bytes used).  Raises the first offending image's error once
+    every worker has finished."""
+    n = len(datas)
+    if host is None:
+        host = np.zeros(blob_capacity(datas), np.uint8)
+    assert host.dtype == np.uint8 and host.flags.c_contiguous and host.size >= blob_capacity(datas)
+    run = (lambda fn, *cols: list(map(fn, *cols))) if pool is None else (lambda fn, *cols: _gather(pool, fn, *cols))
+    descs = run(lambda i: entropy_prepare(datas[i], host, i), range(n))
+    offsets, off = [], n * DESC_BYTES
+    for d in descs:
+        offsets.append(off)
+        d.blob_offset = off
+        off += (d.scan_bytes + 15) // 16 * 16
+
+    def copy_scan(i):
+        d = descs[i]
+        host[offsets[i]:offsets[i] + d.scan_bytes] = np.frombuffer(datas[i], np.uint8, d.scan_bytes, d.scan_offset)
+    run(copy_scan, range(n))
+    return host, off
+
+
+def _gather(pool, fn, *cols):
+    """pool.map that lets every worker finish before the first error leaves."""
+    futures = [pool.submit(fn, *args) for args in zip(*cols)]
+    errors = [f.exception() for f in futures]
+    for e in errors:
+        if e is not None:
+            raise e
+    return [f.result() for f in futures]
+
+
+def _tuning(subseq_bytes, tile):
+    if subseq_bytes is None and tile is None:
+        return None
+    return StJpegEntropyTuning(C.sizeof(StJpegEntropyTuning), int(subseq_bytes or 0), int(tile or 0))
+
+
+def entropy_launch(host, used, blob_dev, n, info, coef, quant, status, work, subseq_bytes=None, tile=None):
+    """st_jpeg_entropy_decode_dev on the current stream of blob_dev's device: `host` the blob of build_blob, blob_dev its
+    device copy (enqueued by the caller in front of this), coef / quant / status / work device tensors."""
+    import torch
+    tuning = _tuning(subseq_bytes, tile)
+    with torch.cuda.device(blob_dev.device):
+        rc = _api().st_jpeg_entropy_decode_dev(host.ctypes.data, blob_dev.data_ptr(), used, n, C.byref(info),
+                                               C.byref(tuning) if tuning is not None else None, coef.data_ptr(),
+                                               quant.data_ptr(), status.data_ptr(), work.data_ptr(),
+                                               work.numel() * work.element_size(),
+                                               torch.cuda.current_stream(blob_dev.device).cuda_stream)
+    _check(rc, 'st_jpeg_entropy_decode_dev')
+
+
+def entropy_decode_device(datas, device, subseq_bytes=None, tile=None):
+    """Test and bench facing: the device entropy decode of N files of one geometry on `device` ->
+    (StJpegInfo, coef int16 (N, coef_count), quant int16 (N, 3, 64) holding the uint16 bit patterns, status int32 (N,),
+    stats int32 (N, 4): tiles, subsequences, max passes, sum of passes), all device tensors, enqueued on the current
+    stream.  subseq_bytes / tile: the tuning (None: the library's defaults)."""
+    import torch
+    datas = [bytes(d) for d in datas]
+    if not datas:
+        raise ValueError('entropy_decode_device: no images')
+    infos = [_info(d) for d in datas]
+    info = infos[0]
+    for i, other in enumerate(infos):
+        if not JpegDecoder._same_geometry(info, other):
+            raise ValueError(f'entropy_decode_device: image {i} differs from image 0 in geometry or sampling class')
+    dev = torch.device(device)
+    n, count = len(datas), int(info.coef_count)
+    host, used = build_blob(datas, torch.empty(blob_capacity(datas), dtype=torch.uint8).pin_memory().numpy())
+    blob_dev = torch.empty(used, dtype=torch.uint8, device=dev)
+    coef = torch.empty((n, count), dtype=torch.int16, device=dev)
+    quant = torch.empty((n, 3, 64), dtype=torch.int16, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    work = torch.empty(int(_api().st_jpeg_entropy_work_bytes(C.byref(info), n)), dtype=torch.uint8, device=dev)
+    pinned = torch.from_numpy(host)
+    blob_dev.copy_(pinned[:used], non_blocking=True)
+    entropy_launch(host, used, blob_dev, n, info, coef, quant, status, work, subseq_bytes, tile)
+    stats = work[:16 * n].view(torch.int32).reshape(n, 4).clone()
+    torch.cuda.current_stream(dev).synchronize()         # the page-locked blob is this call's own: keep it until the copy is done
+    return info, coef, quant, status, stats
 
 
 def reconstruct_host(coef, quant, info, order='rgb', planar=False):
@@ -366,13 +490,21 @@ class JpegDecoder:
     two reconstruction launches on the CURRENT stream, and returns without waiting for the device.  `slots` staging
     slots (page-locked host memory, its device twin and the component-plane work memory) alternate, each guarded by an
     event recorded behind the launches: the host waits only when it is `slots` calls ahead, and a slot's device memory
-    is reused on another stream only behind that event."""
+    is reused on another stream only behind that event.
 
-    def __init__(self, device=None, threads=4, slots=2):
+    entropy='device' (opt-in): the host threads only parse the headers and copy the raw scan bytes into
+    ONE page-locked blob; the Huffman decode runs in HIP (csrc/jpeg_entropy.hip) in front of the reconstruction, with
+    coefficients, tables and accept / refuse verdict equal to the host routine's."""
+
+    def __init__(self, device=None, threads=4, slots=2, entropy='host'):
         import torch
         from concurrent.futures import ThreadPoolExecutor
         if not torch.cuda.is_available():
             raise RuntimeError('JpegDecoder reconstructs on the GPU (st_jpeg_reconstruct); no GPU here - read_jpeg is the host path')
+        if entropy not in ('host', 'device'):
+            raise ValueError(f"JpegDecoder: entropy is 'host' or 'device', not {entropy!r}")
+        self.entropy = entropy
+        self.last_status = None                                # entropy='device': the last call's per-image status words
         dev = torch.device('cuda') if device is None else torch.device(device)
         if dev.type != 'cuda':
             raise ValueError(f'JpegDecoder decodes on a GPU, not on {dev}')
@@ -380,7 +512,7 @@ class JpegDecoder:
         self.dev = torch.device('cuda', torch.cuda.current_device() if dev.index is None else dev.index)
         self.threads = min(max(int(threads), 1), 16)           # never sized from the machine's CPU count
         self._pool = ThreadPoolExecutor(max_workers=self.threads)
-        self._slots = [dict(pin=None, dev=None, work=None, done=torch.cuda.Event(), used=False)
+        self._slots = [dict(pin=None, dev=None, work=None, blob=None, ework=None, done=torch.cuda.Event(), used=False)
                        for _ in range(max(int(slots), 1))]
         self._k = 0
         _api()
@@ -393,10 +525,51 @@ class JpegDecoder:
     def _same_geometry(a, b):
         return (a.height, a.width, a.components, a.sampling) == (b.height, b.width, b.components, b.sampling)
 
-    def decode(self, datas, out=None, order='bgr'):
+    def _decode_device_entropy(self, sl, datas, info, out, order, check, cur):
+        """entropy='device': header parse on the pool, ONE page-locked blob (descriptors + raw scan bytes), ONE
+        non-blocking H2D copy, the entropy launches and st_jpeg_reconstruct on the current stream."""
+        import torch
+        n, count = len(datas), int(info.coef_count)
+        coef_bytes, nbytes = n * count * 2, n * count * 2 + n * 384
+        cap = blob_capacity(datas)
+        if sl['blob'] is None or sl['blob'][0].numel() < cap:
+            sl['blob'] = (torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device=self.dev))
+        if sl['dev'] is None or sl['dev'].numel() < nbytes:    # coefficients and tables: device memory only
+            sl['dev'] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        work_bytes = int(_api().st_jpeg_work_bytes(C.byref(info), n))
+        if sl['work'] is None or sl['work'].numel() < work_bytes:
+            sl['work'] = torch.empty(work_bytes, dtype=torch.uint8, device=self.dev)
+        ework_bytes = int(_api().st_jpeg_entropy_work_bytes(C.byref(info), n))
+        if sl['ework'] is None or sl['ework'].numel() < ework_bytes:
+            sl['ework'] = torch.empty(ework_bytes, dtype=torch.uint8, device=self.dev)
+        pinned, blob_dev = sl['blob']
+        host, used = build_blob(datas, pinned.numpy(), self._pool)
+        status = torch.empty(n, dtype=torch.int32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            blob_dev[:used].copy_(pinned[:used], non_blocking=True)
+            coef, quant = sl['dev'][:coef_bytes], sl['dev'][coef_bytes:nbytes]
+            entropy_launch(host, used, blob_dev, n, info, coef, quant, status, sl['ework'])
+            _check(_api().st_jpeg_reconstruct(coef.data_ptr(), quant.data_ptr(), n, C.byref(info), sl['work'].data_ptr(),
+                                              sl['work'].numel(), out.data_ptr(), out.stride(0), out.stride(1),
+                                              out.stride(2), int(order == 'rgb'), cur.cuda_stream), 'st_jpeg_reconstruct')
+            sl['done'].record(cur)
+        sl['used'] = True
+        self.last_status = status
+        if check:
+            refused = torch.nonzero(status.cpu()).flatten().tolist()       # waits for the N status words
+            if refused:
+                i = refused[0]
+                entropy_decode(datas[i])                       # the host's own ValueError and message
+                raise RuntimeError(f'JpegDecoder.decode: the device refused the entropy data of image {i} (status '
+                                   f'{int(status[i])}) which the host routine accepts')
+
+    def decode(self, datas, out=None, order='bgr', check=True):
         """datas: a sequence of N JPEG byte strings of ONE geometry and sampling class -> torch.uint8 (N, 3, h, w) on the
         device, planes in `order` ('bgr' | 'rgb'), produced on the current stream.  out: write there instead of a fresh
-        allocation (a (N,3,h,w) uint8 device view with unit stride along w; it may sit inside a wider buffer)."""
+        allocation (a (N,3,h,w) uint8 device view with unit stride along w; it may sit inside a wider buffer).
+        entropy='device' only: with check=True the call waits for the N status words and raises the host routine's
+        ValueError for the first refused image; with check=False nothing waits and `last_status` (device int32 (N,),
+        0 = accepted) is the caller's to read."""
         import torch
         if order not in ('bgr', 'rgb'):
             raise ValueError("order is 'bgr' or 'rgb'")
@@ -425,6 +598,9 @@ class JpegDecoder:
         if sl['used']:
             sl['done'].synchronize()         # the copy that last read this staging slot has finished
             cur.wait_event(sl['done'])       # ... and, on whatever stream that was, the launches that used its device memory
+        if self.entropy == 'device':
+            self._decode_device_entropy(sl, datas, info, out, order, check, cur)
+            return out
         if sl['pin'] is None or sl['pin'].numel() < nbytes:
             sl['pin'] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
             sl['dev'] = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
