@@ -15,8 +15,13 @@ Un-vendored third-party pieces restated from their published behaviour [upstream
   lap.lapjv                  -> oracle/lapjv.py
   mmengine InstanceData      -> `Instances` (attribute bag)
 
-PARITY PINNING: the reference holds no fixture for this path and cannot be imported here; pinned
-by its own in-tree source text for everything except the three third-party pieces above ("parity unpinned").
+PARITY PINNING: the reference holds no fixture for this path and `import mmtrack` fails without mmcv /
+mmengine / mmdet, but its in-tree modules execute unmodified under stand-ins for those roots
+(tests/golden/make_reference_golden.py).  This file is held, bit for bit, to what they return - KalmanFilter step by step,
+OCSORTTracker_Disparity.track frame by frame (ids, boxes, scores, depth, scales) and the live tracks' Kalman state after
+the last frame - by tests/test_cpu_reference_fixtures.py on tests/golden/reference/{kalman,tracker}.npz.  The third-party
+pieces above stay "parity unpinned": in those recordings they are THIS file's `Dict`, `Instances`, `bbox_overlaps` and
+oracle/lapjv.py (every recorded stream also reproduces under a second solver, so no row depends on lapjv's tie order).
 
 numpy note: the reference's environment pins scipy<=1.7.3 / Python 3.9 (requirements/runtime.txt:12,
 reproducibility.md:361-365), i.e. numpy 1.x VALUE-BASED casting: `python_float * np.float32_scalar` is float64

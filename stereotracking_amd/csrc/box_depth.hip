@@ -10,7 +10,9 @@
 // numpy semantics that are reproduced on purpose (SURVEY.md §7 "hard parts"):
 //   * box.astype(np.int) truncates toward zero; slice bounds follow Python slice normalisation
 //     (negative indices wrap, out-of-range clamps, start >= stop => empty)
-//   * valid = 0 < depth < 150 on depth = (baseline*focal) / (disp + 1e-6) (fp32, IEEE divide)
+//   * valid = 0 < depth < 150 on depth = (1 / (disp + 1e-6)) * (baseline*focal): fp32, an IEEE reciprocal and then a
+//     product (two roundings).  torch evaluates `python_float / tensor` as tensor.reciprocal() * python_float, so this
+//     is what the reference's disp2depth holds; the single divide bf / (disp + 1e-6) is 1 ulp away on about 1 pixel in 4
 //   * len == 0 or (x2 - x1) > 800                      => depth -1, scale 1
 //   * median = sorted[len // 2]; 4 corner 2x2 means on the RAW depth (empty slice => NaN,
 //     NaN > median is False)
@@ -54,7 +56,7 @@ __device__ __forceinline__ int py_slice_index(int i, int len) {
 }
 
 __device__ __forceinline__ float to_depth(float v, float bf, int is_depth) {
-  return is_depth ? v : bf / (v + 1e-6f);
+  return is_depth ? v : (1.0f / (v + 1e-6f)) * bf;   // torch's scalar / tensor: reciprocal, then the product
 }
 
 __device__ __forceinline__ bool depth_valid(float d) { return d < 150.0f && d > 0.0f; }

@@ -25,6 +25,9 @@ class KalmanFilter:
         self._w_vel = 1.0 / 160
 
     def _stds(self, h, k_pos, k_vel, aspect_pos, aspect_vel):
+        # float(): the reference's numpy 1.x makes `python_float * np.float32` a float64 product, numpy >= 2 (NEP 50) a
+        # float32 one.  The trackers hand over float64 boxes; a float32 box from another caller gets the same covariance.
+        h = float(h)
         p, v = k_pos * self._w_pos * h, k_vel * self._w_vel * h
         return [p, p, aspect_pos, p, v, v, aspect_vel, v]
 
@@ -42,7 +45,7 @@ class KalmanFilter:
         return new_mean, new_cov
 
     def project(self, mean, covariance, bbox_score=0.):
-        p = self._w_pos * mean[3]
+        p = self._w_pos * float(mean[3])
         std = [p, p, 1e-1, p]
         if self.use_nsa:
             std = [(1 - bbox_score) * x for x in std]

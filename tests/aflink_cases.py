@@ -51,6 +51,44 @@ def candidates(rows):
     return infos, pairs, ref.inputs(infos, pairs)
 
 
+AFLINK_SHAPES = tuple(
+    [(f'TemporalModule_{m}.{l}.conv.weight', (co, ci, 7, 1)) for m in (1, 2)
+     for l, (ci, co) in enumerate(((1, 32), (32, 64), (64, 128), (128, 256)))] +
+    [(f'FusionBlock_{m}.conv.weight', (256, 256, 1, 3)) for m in (1, 2)] +
+    [('classifier.fc1.weight', (128, 512)), ('classifier.fc1.bias', (128,)),
+     ('classifier.fc2.weight', (2, 128)), ('classifier.fc2.bias', (2,))])
+AFLINK_NORMS = tuple([(f'TemporalModule_{m}.{l}.{bn}', c) for m in (1, 2) for l, c in enumerate((32, 64, 128, 256))
+                      for bn in ('bnf', 'bnx', 'bny')] + [(f'FusionBlock_{m}.bn', 256) for m in (1, 2)])
+
+
+def recipe_state_dict(seed):
+    """The link network's state dict (reference naming) from numpy's legacy RandomState, whose stream is frozen: the same
+    bytes on every machine and under every torch.  tests/golden/reference/aflink.npz is recorded with these weights (a
+    stored state dict would be 4.2 MB) and keeps their sha256 (state_dict_sha256 below)."""
+    rng = np.random.RandomState(seed)
+    sd = {}
+    for name, shape in AFLINK_SHAPES:
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else 1
+        scale = np.float32(np.sqrt(2.0 / fan_in)) if len(shape) > 1 else np.float32(0.05)
+        sd[name] = torch.from_numpy(rng.standard_normal(shape).astype(np.float32) * scale)
+    for prefix, c in AFLINK_NORMS:
+        sd[prefix + '.weight'] = torch.from_numpy(rng.uniform(0.5, 1.5, c).astype(np.float32))
+        sd[prefix + '.bias'] = torch.from_numpy((rng.standard_normal(c) * 0.1).astype(np.float32))
+        sd[prefix + '.running_mean'] = torch.from_numpy((rng.standard_normal(c) * 0.1).astype(np.float32))
+        sd[prefix + '.running_var'] = torch.from_numpy(rng.uniform(0.5, 1.5, c).astype(np.float32))
+        sd[prefix + '.num_batches_tracked'] = torch.zeros((), dtype=torch.long)
+    return sd
+
+
+def state_dict_sha256(sd):
+    import hashlib
+    h = hashlib.sha256()
+    for k in sorted(sd):
+        if not k.endswith('num_batches_tracked'):
+            h.update(k.encode() + np.ascontiguousarray(sd[k].numpy()).tobytes())
+    return h.hexdigest()
+
+
 @functools.lru_cache(maxsize=None)
 def case(seed=0, n_tracks=70):
     """dict(state_dict, rows, infos, pairs, x, conf64, conf32, logits64, logits32, ref_err, logit_err, threshold).

@@ -5,7 +5,10 @@ mmtrack/models/mot/ocsort_disparity.py extract_depth; line-by-line restatement: 
 the rules below.  DESIGN.md section 11.
 
 Front end, shared with the default extract_depth (oracle/depth.py):
-  R1  depth map: disparity input -> depth = float32(baseline * focal) / (disp + float32(1e-6)), fp32 IEEE divide;
+  R1  depth map: disparity input -> depth = (float32(1) / (disp + float32(1e-6))) * float32(baseline * focal): an fp32
+      IEEE reciprocal, then the product (two roundings).  torch evaluates `python_float / tensor` as
+      tensor.reciprocal() * python_float, so this is the reference's disp2depth bit for bit
+      (tests/golden/reference/depth.npz); one divide bf / (disp + 1e-6) is 1 ulp away on about one pixel in four;
       gt-depth input (baseline < 0 at the ABI) -> the raw map as given.  Channel 0 of (C, H, W), H x W = the padded
       map the model holds.
   R2  box.astype(np.int): every coordinate truncated toward zero.
@@ -67,7 +70,7 @@ def depth_map(disp, baseline=0.25, focal=640.0, is_depth=False):
     if is_depth:
         return d
     bf = np.float32(float(baseline) * float(focal))
-    return (bf / (d + np.float32(1e-6))).astype(np.float32)
+    return ((np.float32(1.0) / (d + np.float32(1e-6))) * bf).astype(np.float32)
 
 
 def _mean64(a):

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Generates the golden fixtures in this directory FROM THE ORACLE (oracle/), on the CPU.
 
-The reference cannot be imported here or on the GPU box (mmcv/mmdet/mmyolo/mmengine absent) and
-ships no fixtures of its own, so these vectors pin the oracle, not the reference:
+`import mmtrack` fails here and on the GPU box (mmcv/mmdet/mmyolo/mmengine absent) and the reference
+ships no fixtures of its own, so these vectors pin the oracle, not the reference (what the reference's own in-tree
+modules return is recorded by make_reference_golden.py into tests/golden/reference/, and the oracle is held to that):
   detector_tiny.npz    head rows of the CPU PyTorch oracle, tiny two-branch YOLOX (widen .375), 1x64x96
   decode_nms.npz       C-oracle decode+NMS on a seeded random head (840 priors x 2 images)
   box_depth.npz        numpy restatement of extract_depth (reference ocsort_disparity.py:136-175) on a

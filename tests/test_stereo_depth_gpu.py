@@ -282,9 +282,8 @@ def test_pack_raw_inputs_matches_reference_pipeline(h, w, cuda):
         gm.current().track(out[key])
     H, W = 64, 96
     # numpy restatement of the reference transforms
-    disp = code.astype(np.float32)
-    disp[code == 65535] = 0
-    disp = disp / 16.
+    from loader_ref import post_processing_v2
+    disp = post_processing_v2(code)     # held to the reference's recorded output by tests/test_cpu_reference_fixtures.py
     ref_img = np.full((N, 3, H, W), 0, np.float32)
     ref_img[:, :, :h, :w] = img
     ref_img[:, :, h:, :] = 114.0
