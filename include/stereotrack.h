@@ -15,6 +15,11 @@
  *     (PyTorch); the library owns only packed weights (freed by *_destroy).
  *   - all work is enqueued on the caller's stream (a hipStream_t passed as
  *     void*); no call synchronises the device or allocates on the hot path.
+ *   - pointer contract (DESIGN.md "Pointer contract"): a device pointer is aligned to its element at least.  Where a
+ *     kernel moves 16 bytes at a time the entry either takes a scalar kernel for a pointer (stride, offset) that is
+ *     not 16-byte aligned - same results, bit for bit - or refuses it with ST_ERR_INVALID before anything is
+ *     launched; which of the two is said at the entry.  Packed weights, biases and workspaces are always 16-byte
+ *     aligned (8 bytes where a workspace holds 64-bit fields only).
  *   - activations are fp32.  Internal activation layout is NHWC
  *     (pixel-major, channel-contiguous); the boundary tensors keep the
  *     reference's NCHW layout.
@@ -82,6 +87,8 @@ typedef struct StConvDesc {
   const float* wgt_wino_dev;
 } StConvDesc;
 
+/* in_dev and wgt_dev must be 16-byte aligned, Cin / in_ld / in_off multiples of 4 (ST_ERR_INVALID otherwise); the
+ * output, upsample and residual tensors of the tile instances take any float alignment, stride and offset. */
 int st_conv2d_nhwc(const StConvDesc* d, st_stream_t stream);
 /* The same convolution with the kernel instance chosen by the caller instead of the library's heuristic:
  * variant 0..21 = tile instances of the implicit-GEMM kernel (st_conv_variant_name), 41 = streaming 1x1 kernel,
@@ -90,7 +97,10 @@ int st_conv2d_nhwc(const StConvDesc* d, st_stream_t stream);
  * 128->128, 256->128), -1 = heuristic.  Returns ST_ERR_INVALID when the instance cannot run this layer (tile
  * does not divide the padded Cout, ...), so callers can autotune per layer by timing the valid ones — which is
  * what st_detector_autotune does internally and StereoCostVolume.autotune does for the aggregation convs.
- * Results are the same convolution for every valid variant (fp32 rounding differs with the summation order). */
+ * Results are the same convolution for every valid variant (fp32 rounding differs with the summation order).
+ * Instances 41 .. 46 also return ST_ERR_INVALID for a tensor, weight or bias pointer that is not 16-byte aligned (41:
+ * in_dev and wgt_dev; its outputs and residual take a scalar epilogue) and for strides / offsets that are not
+ * multiples of 4. */
 int st_conv2d_nhwc_variant(const StConvDesc* d, st_stream_t stream, int variant);
 /* Winograd form of a 3x3 weight tensor.  packed_wgt_host: the [CoutPad][Kpad] matrix st_conv_pack_weights produced
  * (host memory); out_host: st_wino_packed_floats(Cout, Cin) floats, to be uploaded and passed as wgt_wino_dev.
@@ -148,6 +158,7 @@ int st_conv_pack_weights(const float* w, const float* conv_bias, /* may be NULL 
  * 2. Input packing: NCHW fp32 image -> Focus (space-to-depth) NHWC 12-ch.
  *    Replaces mmdet Focus slicing, reference
  *    csp_darknet_disparity_v1.py:104-111 (order TL,BL,TR,BR).
+ *    H, W even; the image 8-byte and the output 16-byte aligned (ST_ERR_INVALID otherwise).
  * ---------------------------------------------------------------------- */
 int st_focus_pack(const float* img_nchw_dev, int N, int C, int H, int W,
                   float* out_nhwc_dev, st_stream_t stream);
@@ -155,7 +166,9 @@ int st_focus_pack(const float* img_nchw_dev, int N, int C, int H, int W,
 /* Fused Focus + stem ConvModule: Focus(x) followed by the 3x3/s1/p1 ConvModule over its 12 channels is a
  * 6x6/s2/p2 convolution of the planar 3-channel image, computed here in one kernel (no NHWC 12-channel
  * intermediate).  Replaces csp_darknet_disparity_v1.py:104-111 (`Focus(3, c, kernel_size=3)`, both the RGB
- * `stem` and the `disp_stem`) as run at :176-179.  Cout <= 64; H even, W a multiple of 4, image 16-byte aligned.
+ * `stem` and the `disp_stem`) as run at :176-179.  Cout <= 64; H even, W a multiple of 4, image and bias 16-byte aligned
+ * (ST_ERR_INVALID otherwise); an output that is not 16-byte aligned, or whose out_ld / out_off / Cout is not a multiple
+ * of 4, is written by scalar stores - same values.
  *   w            stem conv weight [Cout][12][3][3], channels in Focus order (TL,BL,TR,BR groups of 3)
  *   wgt_out      st_stem_packed_floats(Cout) floats, bias_out round_up(Cout,32) floats (host buffers)
  *   out_nhwc_dev [N][H/2][W/2][out_ld], channels written at [out_off, out_off + Cout)          */
@@ -221,7 +234,8 @@ int st_rectify_remap(const void* const* src_dev_ptrs_host, int F, int P, int h, 
 
 /* SPP: out[..., 0:C]=x, [C:2C]=maxpool5, [2C:3C]=maxpool9, [3C:4C]=maxpool13
  * (stride 1, same pad, -inf padding).  x may alias out channels [0,C).
- * Replaces mmyolo SPPFBottleneck pooling, csp_darknet_disparity_v1.py:137-144 */
+ * Replaces mmyolo SPPFBottleneck pooling, csp_darknet_disparity_v1.py:137-144.  C, strides and offsets multiples
+ * of 4, x_dev and out_dev 16-byte aligned (ST_ERR_INVALID otherwise). */
 int st_spp_pool(const float* x_dev, int x_ld, int x_off, int N, int H, int W, int C,
                 float* out_dev, int out_ld, int out_off, st_stream_t stream);
 
@@ -289,7 +303,8 @@ int st_detector_level_info(const StDetector* det, int level, int* h, int* w, int
                            size_t* float_offset);
 /* img/disp: NCHW fp32 [N][3][H][W] device pointers (the tensors
  * TrackDataPreprocessor_Disparity_V1 produces, reference
- * data_preprocessor_disparity_v1.py:21-84). */
+ * data_preprocessor_disparity_v1.py:21-84).  Every device pointer of the forward entries (images, workspace, head
+ * output) must be 16-byte aligned: ST_ERR_INVALID before the first launch otherwise. */
 int st_detector_forward(StDetector* det, const float* img_dev, const float* disp_dev,
                         void* workspace_dev, size_t workspace_bytes, st_stream_t stream,
                         float* head_out_dev);
@@ -418,7 +433,9 @@ size_t st_decode_nms_workspace_bytes(const StDecodeDesc* d);
  * the bit-exact identity of a kept box), out_count[n] = number kept (may exceed
  * max_det: then only the first max_det are stored - the reference applies NO cap under
  * yolox_style=True, so callers must treat out_count[n] > max_det as an overflow and re-run with a
- * larger buffer or raise; rows past min(count, max_det) are written as zero, prior index -1). */
+ * larger buffer or raise; rows past min(count, max_det) are written as zero, prior index -1).
+ * workspace_dev and out_boxes_dev must be 16-byte aligned; with 1..3 classes (8-float rows) head_out_dev too, and every
+ * level_offset a multiple of 4 (ST_ERR_INVALID, nothing launched, otherwise). */
 int st_decode_nms(const StDecodeDesc* d, const float* head_out_dev, void* workspace_dev,
                   size_t workspace_bytes, st_stream_t stream, float* out_boxes_dev,
                   float* out_scores_dev, int64_t* out_labels_dev, int32_t* out_prior_idx_dev,
@@ -431,6 +448,10 @@ int st_decode_nms(const StDecodeDesc* d, const float* head_out_dev, void* worksp
  *    featL/featR: NHWC [N][Hf][Wf][C].  cost[d] = (1/C) sum_c L[x,c]*R[x-d,c]
  *    (0 where x-d<0); disp_lowres = sum_d d*softmax_d(temperature*cost[d]).
  *    out_cost_dev (optional) receives the materialised volume [N][Hf][Wf][D].
+ *    featL_dev / featR_dev must be 16-byte aligned, C and feat_ld multiples of 4
+ *    (ST_ERR_INVALID otherwise).  The volume pointers (out_cost_dev here, cost_dev
+ *    of st_softargmin, disp_postp_dev of st_disp_upsample_pack) take any float
+ *    alignment: one that is not 16-byte aligned runs a scalar kernel, same bits.
  * ---------------------------------------------------------------------- */
 int st_costvolume_softargmin(const float* featL_dev, const float* featR_dev, int N, int Hf,
                              int Wf, int C, int feat_ld, int D, float temperature,
@@ -509,6 +530,9 @@ int st_feat_upsample(const float* feat_dev, int N, int Hf, int Wf, int C, int fe
  *    img_pitch floats.  boxes [N][max_det][4], counts[N].
  *    outputs: depth[N][max_det] (-1 = no valid depth), scale[N][max_det],
  *    scaled_boxes[N][max_det][4].
+ *    boxes_dev and out_scaled_boxes_dev (box rows move as 16 bytes) must be
+ *    16-byte aligned, as boxes_dev / scaled_boxes_dev of st_pack_records
+ *    (ST_ERR_INVALID otherwise).
  * ---------------------------------------------------------------------- */
 size_t st_box_depth_workspace_bytes(int N, int max_det, int H, int W);
 int st_box_depth(const float* disp_dev, size_t img_pitch, int N, int H, int W,
@@ -677,7 +701,8 @@ int st_batched_tracker_get_states(const StBatchedTracker* t, const void* state_d
  *            (the 2 x 3 warp in the coordinates of the (img_h, img_w) crop), via flow, per-cell medians and a
  *            deterministic exhaustive consensus similarity fit (stated deviation from cv2's RANSAC); mesh_out
  *            (optional, N x points x 4: src x, y, dst x, y) and inliers_out (optional, N x points uint8).
- *   ws: caller-owned device workspace of st_cmc_workspace_bytes(N).  Enqueued on `stream`, no host sync.
+ *   ws: caller-owned device workspace of st_cmc_workspace_bytes(N), 8-byte aligned for the entries that fit (it holds
+ *            64-bit keys; ST_ERR_INVALID otherwise).  Enqueued on `stream`, no host sync.
  * ---------------------------------------------------------------------- */
 #define ST_CMC_SIDE 255
 #define ST_CMC_WARP_FLOATS 8
@@ -1159,7 +1184,8 @@ int st_aflink_run(const StAflinkArgs* args, const void* weights, st_stream_t str
  *            warp in IMAGE coordinates} (a failed estimate: {0, 0, identity}) and, optionally, the iterations run
  *            (N,) int32.  All num_iters rounds are enqueued on `stream`; no host sync.  Bit-identical from run to run,
  *            and a pair's row does not depend on N.
- *   ws: caller-owned device workspace of st_cmc_ecc_workspace_bytes(N, plane_h, plane_w).
+ *   ws: caller-owned device workspace of st_cmc_ecc_workspace_bytes(N, plane_h, plane_w), 16-byte aligned
+ *            (ST_ERR_INVALID otherwise).
  *   Every call refuses, before any launch (ST_ERR_INVALID, nothing written): a struct_size mismatch, a null pointer,
  *   a short workspace, a warp_mode / downscale / gauss_filt_size outside its set, num_iters < 1, a plane side under 8
  *   (and N outside 1..65535, a NaN stop_eps, num_iters > 1000 in the estimate: 2 launches are enqueued per round).

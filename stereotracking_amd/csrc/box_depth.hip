@@ -554,6 +554,9 @@ extern "C" int st_pack_records(const float* boxes_dev, const float* scores_dev, 
                  out_records_dev, "st_pack_records: null pointer");
   ST_REQUIRE(mode >= 0 && mode <= 2 && (mode != 2 || prior_idx_dev), "st_pack_records: bad mode");
   ST_REQUIRE(N > 0 && max_det > 0 && n_real >= 0, "st_pack_records: bad geometry");
+  // the two box rows of a detection are read as one 16-byte load each
+  ST_REQUIRE(((reinterpret_cast<uintptr_t>(boxes_dev) | reinterpret_cast<uintptr_t>(scaled_boxes_dev)) & 15) == 0,
+             "st_pack_records: boxes_dev and scaled_boxes_dev must be 16-byte aligned");
   const long long total = (long long)N * (max_det + 1);
   const int blocks = (int)std::min<long long>((total + 255) / 256, 2048);
   hipLaunchKernelGGL(pack_records_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), boxes_dev,
@@ -577,6 +580,9 @@ int box_depth_launch(const float* disp_dev, size_t img_pitch, int N, int H, int 
   ST_REQUIRE(img_pitch >= (size_t)H * W, "st_box_depth: img_pitch smaller than one image");
   ST_REQUIRE(method >= ST_DEPTH_REFERENCE && method <= ST_DEPTH_CENTER, "st_box_depth_method: unknown method %d",
              method);
+  // a box row is read and a scaled box row written as one 16-byte access
+  ST_REQUIRE(((reinterpret_cast<uintptr_t>(boxes_dev) | reinterpret_cast<uintptr_t>(out_scaled_boxes_dev)) & 15) == 0,
+             "st_box_depth: boxes_dev and out_scaled_boxes_dev must be 16-byte aligned");
   // baseline < 0 selects "input is already a depth map" (reference passes gt depth_postp that way,
   // ocsort_disparity.py:120-122); bf = baseline * focal as a Python float product rounded to fp32
   const int is_depth = baseline < 0.f;

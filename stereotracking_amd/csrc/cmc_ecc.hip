@@ -456,6 +456,7 @@ int require_args(const char* who, const StEccParams* prm, int N, int img_h, int 
   using namespace st;
   ST_REQUIRE(prm && prm->struct_size == (int)sizeof(StEccParams), "%s: params struct_size mismatch", who);
   ST_REQUIRE(a && b && ws, "%s: null pointer", who);
+  ST_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned", who);   // float4 gradients
   ST_REQUIRE(N > 0 && N <= 65535 && img_h > 0 && img_w > 0, "%s: bad argument", who);
   ST_REQUIRE(prm->warp_mode >= ST_ECC_TRANSLATION && prm->warp_mode <= ST_ECC_AFFINE,
              "%s: warp_mode %d is not TRANSLATION, EUCLIDEAN or AFFINE", who, prm->warp_mode);

@@ -731,6 +731,7 @@ int require_estimate_args(const char* who, const StCmcParams* prm, int N, int im
   using namespace st;
   ST_REQUIRE(prm && prm->struct_size == (int)sizeof(StCmcParams), "%s: params struct_size mismatch", who);
   ST_REQUIRE(warps_out_dev && ws && N > 0 && img_h > 0 && img_w > 0, "%s: bad argument", who);
+  ST_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "%s: workspace must be 8-byte aligned", who);   // 64-bit fit keys
   ST_REQUIRE(prm->step >= 8 && prm->step * prm->step <= 256, "%s: step %d must be in 8..16", who, prm->step);
   ST_REQUIRE(ws_bytes >= st_cmc_workspace_bytes(N), "%s: workspace %zu < %zu bytes", who, ws_bytes,
              st_cmc_workspace_bytes(N));
@@ -789,6 +790,7 @@ extern "C" int st_cmc_fit(const float* points_dev, int N, int P, float ransac_th
                           size_t ws_bytes, float* warps_out_dev, unsigned char* inliers_out_dev, st_stream_t stream) {
   using namespace st;
   ST_REQUIRE(points_dev && warps_out_dev && ws && N > 0, "st_cmc_fit: bad argument");
+  ST_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "st_cmc_fit: workspace must be 8-byte aligned");   // 64-bit fit keys
   ST_REQUIRE(P >= 2 && P <= kMaxPoints, "st_cmc_fit: %d points, must be in 2..%d", P, kMaxPoints);
   ST_REQUIRE(ws_bytes >= st_cmc_workspace_bytes(N), "st_cmc_fit: workspace %zu < %zu bytes", ws_bytes,
              st_cmc_workspace_bytes(N));

@@ -874,6 +874,9 @@ int conv2d_launch(const StConvDesc& d, hipStream_t stream, int force_variant, in
   ST_REQUIRE(d.Cin % 4 == 0 && d.in_ld % 4 == 0 && d.in_off % 4 == 0,
              "conv: Cin/in_ld/in_off must be multiples of 4 (got %d/%d/%d)", d.Cin, d.in_ld,
              d.in_off);
+  // every tile stages its operands in 16-byte buffer loads (into registers or straight into LDS)
+  ST_REQUIRE(((reinterpret_cast<uintptr_t>(d.in_dev) | reinterpret_cast<uintptr_t>(d.wgt_dev)) & 15) == 0,
+             "st_conv2d_nhwc: in_dev and wgt_dev must be 16-byte aligned");
   ST_REQUIRE(d.N > 0 && d.Hi > 0 && d.Wi > 0 && d.Cout > 0 && d.KH > 0 && d.KW > 0 &&
                  d.stride > 0 && d.pad >= 0,
              "conv: bad geometry");

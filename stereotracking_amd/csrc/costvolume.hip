@@ -806,6 +806,9 @@ extern "C" int st_costvolume_softargmin(const float* featL_dev, const float* fea
   ST_REQUIRE(featL_dev && featR_dev && (out_cost_dev || out_disp_dev), "st_costvolume_softargmin: null pointer");
   ST_REQUIRE(N > 0 && Hf > 0 && Wf > 0 && C > 0 && C % 4 == 0 && feat_ld % 4 == 0 && feat_ld >= C,
              "st_costvolume_softargmin: C and feat_ld must be positive multiples of 4");
+  // both kernels gather the features in 16-byte loads, whichever of them out_cost_dev selects below
+  ST_REQUIRE(((reinterpret_cast<uintptr_t>(featL_dev) | reinterpret_cast<uintptr_t>(featR_dev)) & 15) == 0,
+             "st_costvolume_softargmin: featL_dev and featR_dev must be 16-byte aligned");
   ST_REQUIRE(D > 0 && D <= 4 * CV_MAXDG, "st_costvolume_softargmin: D must be in [1, %d]", 4 * CV_MAXDG);
   ST_REQUIRE(Hf <= 65535 && N <= 65535, "st_costvolume_softargmin: grid too large");
   hipStream_t stream = static_cast<hipStream_t>(stream_);

@@ -414,6 +414,16 @@ extern "C" int st_decode_nms(const StDecodeDesc* d, const float* head_out_dev, v
   ST_CHECK(decode_layout(*d, L));
   if (workspace_bytes < L.total)
     return set_error(ST_ERR_WORKSPACE, "st_decode_nms: workspace %zu < required %zu", workspace_bytes, L.total);
+  // 16-byte accesses: the 8-float head rows of 1..3 classes (two loads per prior), the box rows of out_boxes_dev and
+  // the candidate boxes / 8-byte keys inside the workspace
+  ST_REQUIRE(((reinterpret_cast<uintptr_t>(workspace_dev) | reinterpret_cast<uintptr_t>(out_boxes_dev)) & 15) == 0,
+             "st_decode_nms: workspace_dev and out_boxes_dev must be 16-byte aligned");
+  if (L.nc <= 3) {
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(head_out_dev) & 15) == 0,
+               "st_decode_nms: head_out_dev must be 16-byte aligned");
+    for (int l = 0; l < d->num_levels; ++l)
+      ST_REQUIRE(d->level_offset[l] % 4 == 0, "st_decode_nms: level_offset[%d] must be a multiple of 4 floats", l);
+  }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   char* ws = static_cast<char*>(workspace_dev);
   DecodeArgs a{};

@@ -841,6 +841,12 @@ int launch_op(StDetector* det, Op& o, int img0, const float* const inputs[3], fl
 // produced and consumed while still resident in the Infinity Cache.
 int run_ops(StDetector* det, int phase_lo, int phase_hi, const float* const inputs[3], float* ws,
             float* head, hipStream_t stream) {
+  // every op moves 16-byte quads through its tensors; the plan's offsets are multiples of 4 floats, so the bases decide.
+  // Checked once, in front of the first launch (NULL = an input this configuration or phase does not take).
+  ST_REQUIRE(((reinterpret_cast<uintptr_t>(inputs[0]) | reinterpret_cast<uintptr_t>(inputs[1]) |
+               reinterpret_cast<uintptr_t>(inputs[2]) | reinterpret_cast<uintptr_t>(ws) |
+               reinterpret_cast<uintptr_t>(head)) & 15) == 0,
+             "st_detector_forward: img_dev, disp_dev, right_dev, workspace_dev and head_out_dev must be 16-byte aligned");
   const size_t ev_per_op = 2 * (size_t)det->max_group_count;
   if (det->timing && det->events.size() != ev_per_op * det->ops.size()) {
     for (auto& e : det->events) (void)hipEventDestroy(e);

@@ -198,7 +198,8 @@ bool dc_conv_applicable(const StConvDesc& d) {
   if (d.Cin != 32 && d.Cin != 48 && d.Cin != 64) return false;
   if (d.Cout != 32 && d.Cout != 48 && d.Cout != 64) return false;
   if ((d.in_ld | d.in_off | d.out1_ld | d.out1_off) & 3) return false;
-  if ((reinterpret_cast<uintptr_t>(d.in_dev) | reinterpret_cast<uintptr_t>(d.out1_dev)) & 15) return false;
+  if ((reinterpret_cast<uintptr_t>(d.in_dev) | reinterpret_cast<uintptr_t>(d.out1_dev) |
+       reinterpret_cast<uintptr_t>(d.wgt_dev) | reinterpret_cast<uintptr_t>(d.bias_dev)) & 15) return false;
   if (d.res_dev && (((d.res_ld | d.res_off) & 3) || (reinterpret_cast<uintptr_t>(d.res_dev) & 15))) return false;
   const long long M = (long long)d.N * d.Hi * d.Wi, lim = 1ll << 31;
   if (M * d.in_ld * 4 >= lim || M * d.out1_ld * 4 >= lim) return false;

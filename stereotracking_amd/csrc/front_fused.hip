@@ -300,7 +300,8 @@ bool front_fused_applicable(const StConvDesc& a, const StConvDesc& ms, const StC
   if (!a.in_dev || !a.wgt_dev || !a.bias_dev || !ms.bias_dev || !c1.bias_dev) return false;
   if ((a.in_ld | a.in_off | ms.out1_ld | ms.out1_off | ms.out2_ld | ms.out2_off | c1.out1_ld | c1.out1_off) & 3) return false;
   if ((reinterpret_cast<uintptr_t>(a.in_dev) | reinterpret_cast<uintptr_t>(ms.out1_dev) |
-       reinterpret_cast<uintptr_t>(ms.out2_dev) | reinterpret_cast<uintptr_t>(c1.out1_dev)) & 15) return false;
+       reinterpret_cast<uintptr_t>(ms.out2_dev) | reinterpret_cast<uintptr_t>(c1.out1_dev) |
+       reinterpret_cast<uintptr_t>(a.wgt_dev)) & 15) return false;
   const int Ho = (a.Hi - 1) / 2 + 1, Wo = (a.Wi - 1) / 2 + 1;
   if (ms.N != a.N || ms.Hi != Ho || ms.Wi != Wo || c1.N != a.N || c1.Hi != Ho || c1.Wi != Wo) return false;
   const long long Mi = (long long)a.N * a.Hi * a.Wi, Mo = (long long)a.N * Ho * Wo, lim = 1ll << 31;
@@ -312,6 +313,8 @@ bool front_fused_applicable(const StConvDesc& a, const StConvDesc& ms, const StC
 int front_fused_launch(const StConvDesc& da, const StConvDesc& dms, const StConvDesc& dc1, const float* frag_ms_dev,
                        const float* frag_c1_dev, hipStream_t stream) {
   ST_REQUIRE(frag_ms_dev && frag_c1_dev, "fused front: null fragment weights");
+  ST_REQUIRE(((reinterpret_cast<uintptr_t>(frag_ms_dev) | reinterpret_cast<uintptr_t>(frag_c1_dev)) & 15) == 0,
+             "fused front: fragment weights must be 16-byte aligned");
   ST_REQUIRE(front_fused_applicable(da, dms, dc1),
              "fused front: needs conv3x3/s2 32->64 -> 1x1 64->32|32 (split store) -> 1x1 32->32, SiLU, no residual, "
              "16-byte aligned tensors, channel strides multiples of 4");

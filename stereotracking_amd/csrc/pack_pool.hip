@@ -141,6 +141,9 @@ __global__ __launch_bounds__(256) void spp_pool_lds_kernel(const float* __restri
 int focus_pack_launch(const float* img, int N, int C, int H, int W, float* out, hipStream_t stream) {
   ST_REQUIRE(img && out, "focus_pack: null pointer");
   ST_REQUIRE(N > 0 && H > 0 && W > 0 && (H % 2) == 0 && (W % 2) == 0, "focus_pack: H, W must be even");
+  // a thread reads pixel pairs (8 bytes) and writes channel quads (16 bytes)
+  ST_REQUIRE((reinterpret_cast<uintptr_t>(img) & 7) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+             "focus_pack: the image must be 8-byte and the output 16-byte aligned");
   const long long total = (long long)N * (H / 2) * (W / 2);
   const int blocks = (int)std::min<long long>((total + 255) / 256, 256 * 16);
   switch (C) {
@@ -158,6 +161,9 @@ int spp_pool_launch(const float* x, int x_ld, int x_off, int N, int H, int W, in
   ST_REQUIRE(C % 4 == 0 && x_ld % 4 == 0 && x_off % 4 == 0 && out_ld % 4 == 0 && out_off % 4 == 0,
              "spp_pool: channel counts/offsets must be multiples of 4");
   ST_REQUIRE(out_off + 4 * C <= out_ld && x_off + C <= x_ld, "spp_pool: slice exceeds ld");
+  // the sweep kernel of the larger maps moves channel quads (16 bytes) through both pointers
+  ST_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+             "spp_pool: x and out must be 16-byte aligned");
   const int copy_x = !(x == out && x_ld == out_ld && x_off == out_off);
   // small maps (the stride-32 level of the path): whole-map LDS cascade, 8 channels per workgroup
   // channels per workgroup: the cascade is 7 dependent LDS sweeps with barriers, i.e. latency-bound, so small

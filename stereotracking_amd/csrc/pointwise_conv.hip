@@ -188,16 +188,21 @@ __global__ __launch_bounds__(256, 2) void pw_conv_kernel(const PwArgs p) {
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o2rsrc, off2, 0, 0);
           }
         } else {
+          // ONE bit cast of the whole vector: __builtin_bit_cast(unsigned, v[e]) - the cast of a vector-element lvalue -
+          // is compiled to element 0 for every e (tests/test_pointer_contract_gpu.py: the scalar stores equal the 16-byte
+          // ones).  Element-wise reads and writes of a vector (v[e] = x above) are fine.
+          const u32x4 u = __builtin_bit_cast(u32x4, v);
+          const unsigned us[4] = {u[0], u[1], u[2], u[3]};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int c = co + e;
             const bool ok = mv && c < p.Cout, first = c < p.split;
             const unsigned off1 = ok && first ? (unsigned)((m * p.out1_ld + p.out1_off + c) * 4) : 0x80000000u;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[e]), o1rsrc, off1, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(us[e], o1rsrc, off1, 0, 0);
             if (p.out2) {
               const unsigned off2 =
                   ok && !first ? (unsigned)((m * p.out2_ld + p.out2_off + c - p.split) * 4) : 0x80000000u;
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[e]), o2rsrc, off2, 0, 0);
+              __builtin_amdgcn_raw_buffer_store_b32(us[e], o2rsrc, off2, 0, 0);
             }
           }
         }
@@ -227,11 +232,13 @@ __global__ __launch_bounds__(256, 2) void pw_conv_kernel(const PwArgs p) {
           const unsigned off = (mv && co < p.Cout2) ? (unsigned)((m * p.out3_ld + p.out3_off + co) * 4) : 0x80000000u;
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o3rsrc, off, 0, 0);
         } else {
+          const u32x4 u = __builtin_bit_cast(u32x4, v);
+          const unsigned us[4] = {u[0], u[1], u[2], u[3]};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const unsigned off =
                 (mv && co + e < p.Cout2) ? (unsigned)((m * p.out3_ld + p.out3_off + co + e) * 4) : 0x80000000u;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[e]), o3rsrc, off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(us[e], o3rsrc, off, 0, 0);
           }
         }
       }
@@ -282,7 +289,8 @@ bool pw_conv_applicable(const StConvDesc& d) {
   if (d.KH != 1 || d.KW != 1 || d.stride != 1 || d.pad != 0 || d.up_dev) return false;
   if (d.Cin != 32 && d.Cin != 64) return false;
   if (d.Cout < 1 || d.Cout > 64) return false;
-  if (d.in_ld % 4 || d.in_off % 4 || (reinterpret_cast<uintptr_t>(d.in_dev) & 15)) return false;
+  if (d.in_ld % 4 || d.in_off % 4 ||
+      ((reinterpret_cast<uintptr_t>(d.in_dev) | reinterpret_cast<uintptr_t>(d.wgt_dev)) & 15)) return false;
   const long long M = (long long)d.N * d.Hi * d.Wi;
   const long long lim = 1ll << 31;
   if (M * d.in_ld * 4 >= lim || M * d.out1_ld * 4 >= lim) return false;

@@ -234,7 +234,7 @@ bool pwr_conv_applicable(const StConvDesc& d) {
   const int split = d.out2_dev ? d.split : d.Cout;
   if (split < 0 || split > d.Cout || (split & 15)) return false;
   if ((d.in_ld | d.in_off | d.out1_ld | d.out1_off) & 3) return false;
-  if (!al16(d.in_dev) || !al16(d.out1_dev)) return false;
+  if (!al16(d.in_dev) || !al16(d.out1_dev) || !al16(d.wgt_dev)) return false;
   if (d.in_off + d.Cin > d.in_ld || d.out1_off + split > d.out1_ld) return false;
   const long long M = (long long)d.N * d.Hi * d.Wi, lim = 1ll << 31;
   if (M <= 0 || M >= (1ll << 30) || M * d.in_ld * 4 >= lim || M * d.out1_ld * 4 >= lim) return false;
@@ -254,7 +254,7 @@ bool pwr_chain_applicable(const StConvDesc& d, const StConvDesc& c) {
   if (c.KH != 1 || c.KW != 1 || c.stride != 1 || c.pad != 0 || c.up_dev || c.res_dev || c.out2_dev) return false;
   if (c.Cin != 64 || c.Cout != 64 || !c.wgt_dev || !c.bias_dev || !c.out1_dev) return false;
   if (c.N != d.N || c.Hi != d.Hi || c.Wi != d.Wi) return false;
-  if (((c.out1_ld | c.out1_off) & 3) || !al16(c.out1_dev) || c.out1_off + 64 > c.out1_ld) return false;
+  if (((c.out1_ld | c.out1_off) & 3) || !al16(c.out1_dev) || !al16(c.wgt_dev) || c.out1_off + 64 > c.out1_ld) return false;
   return (long long)d.N * d.Hi * d.Wi * c.out1_ld * 4 < (1ll << 31);
 }
 

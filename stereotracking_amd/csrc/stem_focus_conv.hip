@@ -216,10 +216,13 @@ __global__ __launch_bounds__(256, NB == 1 ? 2 : 1) void stem_focus_conv_kernel(c
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v),
                                              orsrc, off, 0, 0);
     } else {
+      // ONE bit cast of the whole vector: __builtin_bit_cast(unsigned, v[e]) - the cast of a vector-element lvalue - is
+      // compiled to element 0 for every e (tests/test_pointer_contract_gpu.py: the scalar stores equal the 16-byte ones)
+      const auto u = __builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const unsigned off = co + e < p.Cout ? pix_off[i] + (co + e) * 4 : 0x80000000u;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[e]), orsrc, off, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(u[e], orsrc, off, 0, 0);
       }
     }
 #else
@@ -325,6 +328,7 @@ int stem_focus_conv_launch(const float* in, int N, int H, int W, int used_planes
   ST_REQUIRE(Cout > 0 && Cout <= 64, "stem_focus_conv: Cout must be in 1..64 (got %d)", Cout);
   ST_REQUIRE(out_off >= 0 && out_off + Cout <= out_ld, "stem_focus_conv: output slice exceeds out_ld");
   ST_REQUIRE(raw || (reinterpret_cast<uintptr_t>(in) & 15) == 0, "stem_focus_conv: input must be 16-byte aligned");
+  ST_REQUIRE((reinterpret_cast<uintptr_t>(bias) & 15) == 0, "stem_focus_conv: bias must be 16-byte aligned");
   StemArgs a;
   for (int i = 0; i < STEM_MAX_FRAMES; ++i) a.frames[i] = raw && i < N ? raw->frames[i] : nullptr;
   a.h = raw ? raw->h : H; a.w = raw ? raw->w : W;

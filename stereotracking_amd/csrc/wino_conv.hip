@@ -868,7 +868,8 @@ bool wino_conv_applicable(const StConvDesc& d) {
   if (d.KH != 3 || d.KW != 3 || d.stride != 1 || d.pad != 1 || d.up_dev || d.out2_dev) return false;
   if (!wino_shape_ok(d.Cin, d.Cout)) return false;
   if ((d.in_ld | d.in_off | d.out1_ld | d.out1_off) & 3) return false;
-  if ((reinterpret_cast<uintptr_t>(d.in_dev) | reinterpret_cast<uintptr_t>(d.out1_dev)) & 15) return false;
+  if ((reinterpret_cast<uintptr_t>(d.in_dev) | reinterpret_cast<uintptr_t>(d.out1_dev) |
+       reinterpret_cast<uintptr_t>(d.wgt_wino_dev) | reinterpret_cast<uintptr_t>(d.bias_dev)) & 15) return false;
   if (d.res_dev && (((d.res_ld | d.res_off) & 3) || (reinterpret_cast<uintptr_t>(d.res_dev) & 15))) return false;
   if (d.Cout % 4) return false;
   const long long M = (long long)d.N * d.Hi * d.Wi, lim = 1ll << 31;

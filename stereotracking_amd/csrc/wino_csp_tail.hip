@@ -371,7 +371,7 @@ bool csp_tail_applicable(const StConvDesc& c2, const StConvDesc& f) {
   const uintptr_t al = reinterpret_cast<uintptr_t>(c2.in_dev) | reinterpret_cast<uintptr_t>(c2.res_dev) |
                        reinterpret_cast<uintptr_t>(f.in_dev) | reinterpret_cast<uintptr_t>(f.out1_dev) |
                        reinterpret_cast<uintptr_t>(f.res_dev) | reinterpret_cast<uintptr_t>(c2.bias_dev) |
-                       reinterpret_cast<uintptr_t>(f.bias_dev);
+                       reinterpret_cast<uintptr_t>(f.bias_dev) | reinterpret_cast<uintptr_t>(c2.wgt_wino_dev);
   if (al & 15) return false;
   const long long M = (long long)c2.N * c2.Hi * c2.Wi, lim = 1ll << 31;
   if (M * c2.in_ld * 4 >= lim || M * c2.res_ld * 4 >= lim || M * f.in_ld * 4 >= lim || M * f.out1_ld * 4 >= lim) return false;

@@ -40,21 +40,25 @@ def min_band(t):
     return (2 * row * t.element_size() + 4096 + 255) // 256 * 256
 
 
-def arena(t, band=None, device=None):
+def arena(t, band=None, device=None, offset_bytes=0):
     """`t`'s shape, strides and values on `device` (default: t's own), inside one uint8 allocation with `band` bytes of
     0xFF before and after it.  band: a multiple of 256 (the bands start on a 256-byte boundary, so the 16-byte
-    alignment the kernels require survives), at least min_band(t)."""
+    alignment the kernels require survives), at least min_band(t).  offset_bytes (0 .. 255, a multiple of the element
+    size): the tensor starts that many bytes past the 256-byte boundary - a pointer the pointer-contract tests hand to
+    an entry point; the band in front of it grows by the same bytes, the band behind it stays whole."""
     band = min_band(t) if band is None else band
     assert band % 256 == 0 and band >= min_band(t), f'band {band}: need a multiple of 256, at least {min_band(t)}'
+    assert 0 <= offset_bytes < 256 and offset_bytes % t.element_size() == 0, f'offset_bytes {offset_bytes}'
     device = t.device if device is None else torch.device(device)
     nbytes = _extent(t) * t.element_size()
-    raw = torch.full((band + nbytes + band + 256,), 0xFF, dtype=torch.uint8, device=device)
+    front = band + offset_bytes
+    raw = torch.full((front + nbytes + band + 256,), 0xFF, dtype=torch.uint8, device=device)
     shift = -raw.data_ptr() % 256       # 0 on the device; host allocations are only 64-byte aligned
-    base = raw[shift:shift + band + nbytes + band]
-    inner = base[band:band + nbytes].view(t.dtype) if nbytes else base[band:band].view(t.dtype)
+    base = raw[shift:shift + front + nbytes + band]
+    inner = base[front:front + nbytes].view(t.dtype) if nbytes else base[front:front].view(t.dtype)
     view = inner.as_strided(t.shape, t.stride())
     view.copy_(t)
-    view._arena = (base, band, nbytes)      # keeps the allocation alive with the view
+    view._arena = (base, front, nbytes)     # keeps the allocation alive with the view
     return view
 
 

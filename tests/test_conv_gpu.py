@@ -31,11 +31,24 @@ def pack(w, bias=None, bn=None, eps=1e-3):
 
 
 def run_conv(x_nchw, w, bias, stride, pad, act, dev, variant=-1, res=None, post_scale=1.0, split=None, up=False,
-             in_ld=None, in_off=0):
+             in_ld=None, in_off=0, out1_off=4, out1_ld=None, out2_off=0, out2_ld=None, res_ld=None, res_off=0,
+             up_ld=None, up_off=0, shift=None, want_status=False):
     """Buffers come from the ambient guard_memory session: finite garbage in the unused channels and plain allocations,
-    unless a guard test (guard_memory.run_both) says otherwise."""
+    unless a guard test (guard_memory.run_both) says otherwise.  The channel slices: out1 at out1_off of out1_ld
+    (default: 4 of s + 4), out2 / res / up at *_off of *_ld (default: 0 of their own width), garbage (-777 in the
+    outputs, randn * 3 in the residual) in the slack.  shift = {'in' | 'wgt' | 'wino' | 'bias' | 'out1' | 'out2' | 'up' | 'res':
+    bytes}: that buffer in an arena, its base pointer that many bytes past a 256-byte boundary (tests/pointer_contract.py).
+    want_status: the call's status comes back first instead of being checked (a refusal leaves the outputs alone)."""
     lib = _lib.load()
     mem = guard_memory.current()
+    shift = shift or {}
+
+    def place(name, t):       # a buffer the session built, or - shifted - the same values in an arena of their own
+        if name not in shift:
+            return t
+        moved = guard_memory.arena(t.cpu(), device=dev, offset_bytes=shift[name])
+        return mem.track(moved) if name in ('out1', 'out2', 'up') else moved
+
     N, Cin, Hi, Wi = x_nchw.shape
     Cout, _, KH, KW = w.shape
     Ho = (Hi + 2 * pad - KH) // stride + 1
@@ -43,9 +56,9 @@ def run_conv(x_nchw, w, bias, stride, pad, act, dev, variant=-1, res=None, post_
     in_ld = in_ld or Cin
     xin = torch.randn(N, Hi, Wi, in_ld) * 3.0  # garbage in the unused channels
     xin[..., in_off:in_off + Cin] = x_nchw.permute(0, 2, 3, 1)
-    xin = mem.input(xin, dev, in_off, Cin)
+    xin = place('in', mem.input(xin, dev, in_off, Cin))
     wp, bp = pack(w, bias)
-    wp, bp = wp.to(dev), bp.to(dev)
+    wp, bp = place('wgt', wp.to(dev)), place('bias', bp.to(dev))
     d = StConvDesc()
     d.in_dev = xin.data_ptr(); d.N, d.Hi, d.Wi, d.Cin, d.in_ld, d.in_off = N, Hi, Wi, Cin, in_ld, in_off
     d.wgt_dev = wp.data_ptr(); d.bias_dev = bp.data_ptr()
@@ -55,37 +68,66 @@ def run_conv(x_nchw, w, bias, stride, pad, act, dev, variant=-1, res=None, post_
         wino = torch.empty(lib.st_wino_packed_floats(Cout, Cin), dtype=torch.float32)
         wp_host = wp.cpu()   # keep alive: ptr() does not hold a reference
         check(lib.st_wino_pack_weights(ptr(wp_host), Cout, Cin, ptr(wino)), 'st_wino_pack_weights')
-        wino = wino.to(dev)
+        wino = place('wino', wino.to(dev))
         d.wgt_wino_dev = wino.data_ptr()
     s = Cout if split is None else split
-    out1 = mem.output((N, Ho, Wo, s + 4), dev)  # ld = s+4, off = 4; filled with -777
-    d.out1_dev = out1.data_ptr(); d.out1_ld, d.out1_off, d.split = s + 4, 4, s
+    out1_ld = s + out1_off if out1_ld is None else out1_ld
+    out1 = place('out1', mem.output((N, Ho, Wo, out1_ld), dev))  # filled with -777
+    d.out1_dev = out1.data_ptr(); d.out1_ld, d.out1_off, d.split = out1_ld, out1_off, s
     out2 = None
     if split is not None:
-        out2 = mem.output((N, Ho, Wo, Cout - s), dev)
-        d.out2_dev = out2.data_ptr(); d.out2_ld, d.out2_off = Cout - s, 0
+        out2_ld = Cout - s + out2_off if out2_ld is None else out2_ld
+        out2 = place('out2', mem.output((N, Ho, Wo, out2_ld), dev))
+        d.out2_dev = out2.data_ptr(); d.out2_ld, d.out2_off = out2_ld, out2_off
     upb = None
     if up:
-        upb = mem.output((N, 2 * Ho, 2 * Wo, Cout), dev)
-        d.up_dev = upb.data_ptr(); d.up_ld, d.up_off = Cout, 0
+        up_ld = Cout + up_off if up_ld is None else up_ld
+        upb = place('up', mem.output((N, 2 * Ho, 2 * Wo, up_ld), dev))
+        d.up_dev = upb.data_ptr(); d.up_ld, d.up_off = up_ld, up_off
     resb = None
     if res is not None:
-        resb = mem.input(res.permute(0, 2, 3, 1), dev)
-        d.res_dev = resb.data_ptr(); d.res_ld, d.res_off = Cout, 0
+        res_ld = Cout + res_off if res_ld is None else res_ld
+        if res_ld == Cout and res_off == 0:
+            resb = place('res', mem.input(res.permute(0, 2, 3, 1), dev))
+        else:
+            rfull = torch.randn(N, Ho, Wo, res_ld) * 3.0  # garbage in the unused channels
+            rfull[..., res_off:res_off + Cout] = res.permute(0, 2, 3, 1)
+            resb = place('res', mem.input(rfull, dev, res_off, Cout))
+        d.res_dev = resb.data_ptr(); d.res_ld, d.res_off = res_ld, res_off
     d.post_scale = post_scale
     d.act = act
     stream = _lib.current_stream()
     if variant >= 0:
-        check(lib.st_conv2d_nhwc_variant(C.byref(d), stream, variant), 'conv')
+        rc = lib.st_conv2d_nhwc_variant(C.byref(d), stream, variant)
     else:
-        check(lib.st_conv2d_nhwc(C.byref(d), stream), 'conv')
+        rc = lib.st_conv2d_nhwc(C.byref(d), stream)
+    if not want_status:
+        check(rc, 'conv')
     torch.cuda.synchronize()
+    if rc != 0:      # refused: nothing was launched, every output cell still holds its fill
+        for o in (out1, out2, upb):
+            assert o is None or torch.all(o.cpu() == -777.0), 'a refused conv wrote an output'
+        assert guard_memory.bands_intact(*[t for t in (xin, wp, bp, wino, out1, out2, upb, resb) if hasattr(t, '_arena')])
+        return rc, None, None
     o1 = out1.cpu()
-    assert torch.all(o1[..., :4] == -777.0), 'kernel wrote outside its channel slice'
-    full = o1[..., 4:]
+    assert torch.all(o1[..., :out1_off] == -777.0) and torch.all(o1[..., out1_off + s:] == -777.0), \
+        'kernel wrote outside its channel slice'
+    full = o1[..., out1_off:out1_off + s]
     if out2 is not None:
-        full = torch.cat([full, out2.cpu()], dim=-1)
-    return full.permute(0, 3, 1, 2), (upb.cpu().permute(0, 3, 1, 2) if upb is not None else None)
+        o2 = out2.cpu()
+        assert torch.all(o2[..., :out2_off] == -777.0) and torch.all(o2[..., out2_off + Cout - s:] == -777.0), \
+            'kernel wrote outside the channel slice of out2'
+        full = torch.cat([full, o2[..., out2_off:out2_off + Cout - s]], dim=-1)
+    upo = None
+    if upb is not None:
+        u = upb.cpu()
+        assert torch.all(u[..., :up_off] == -777.0) and torch.all(u[..., up_off + Cout:] == -777.0), \
+            'kernel wrote outside the channel slice of up'
+        upo = u[..., up_off:up_off + Cout].permute(0, 3, 1, 2)
+    assert guard_memory.bands_intact(*[t for t in (xin, wp, bp, wino, out1, out2, upb, resb) if hasattr(t, '_arena')]), \
+        'a guard band of a shifted buffer was written'
+    out = (full.permute(0, 3, 1, 2), upo)
+    return (rc,) + out if want_status else out
 
 
 def ref_conv(x, w, bias, stride, pad, act, res=None, post_scale=1.0):

@@ -19,19 +19,40 @@ from stereotracking_amd._lib import check, ptr  # noqa: E402
 def test_arena_preserves_values_strides_and_alignment(shape, dtype):
     g = torch.Generator().manual_seed(len(shape))
     t = (torch.rand(shape, generator=g) * 200).to(dtype)
-    a = gm.arena(t)
-    base, band, nbytes = a._arena
+    for offset in (0, 4, 8, 12):        # 0: what every buffer builder asks for; the others: tests/pointer_contract.py
+        _arena_at(t, shape, dtype, offset)
+
+
+def _arena_at(t, shape, dtype, offset):
+    if offset % t.element_size():       # a tensor cannot start between two of its own elements
+        with pytest.raises(AssertionError):
+            gm.arena(t, offset_bytes=offset)
+        return
+    a = gm.arena(t, offset_bytes=offset) if offset else gm.arena(t)     # the default is offset 0
+    base, front, nbytes = a._arena
+    band = front - offset
     assert a.shape == t.shape and a.stride() == t.stride() and a.dtype == t.dtype and torch.equal(a, t)
     assert band % 256 == 0 and band >= gm.min_band(t) and nbytes == t.numel() * t.element_size()
     if t.dim() == 4:      # two rows of an NHWC map (2 * W * ld * 4 bytes) and a K-chunk
         assert band >= 2 * shape[2] * shape[3] * t.element_size() + 4096
-    assert a.data_ptr() % 256 == 0 and a.data_ptr() == base.data_ptr() + band
-    assert base.numel() == 2 * band + nbytes
+    assert a.data_ptr() % 256 == offset and a.data_ptr() == base.data_ptr() + band + offset
+    assert base.data_ptr() % 256 == 0
+    if offset == 0:
+        assert a.data_ptr() % 256 == 0 and a.data_ptr() % 16 == 0
+    else:
+        assert a.data_ptr() % 16 == offset
+    assert base.numel() == 2 * band + offset + nbytes          # both bands whole, the shift on top of the front one
     assert gm.bands_intact(a)
-    assert bool((base[:band] == 0xFF).all()) and bool((base[band + nbytes:] == 0xFF).all())
+    assert bool((base[:front] == 0xFF).all()) and bool((base[front + nbytes:] == 0xFF).all())
+    assert base[front + nbytes:].numel() == band
     if dtype == torch.float32:      # the cell before and the cell after the tensor read as NaN
-        assert torch.isnan(base[band - 4:band].view(torch.float32)).all()
-        assert torch.isnan(base[band + nbytes:band + nbytes + 4].view(torch.float32)).all()
+        assert torch.isnan(base[front - 4:front].view(torch.float32)).all()
+        assert torch.isnan(base[front + nbytes:front + nbytes + 4].view(torch.float32)).all()
+    a.view(-1)[0] = 1                   # a write inside the tensor leaves the bands alone ...
+    assert gm.bands_intact(a)
+    if offset:                          # ... one into the bytes the shift skipped does not
+        base[band] = 0
+        assert not gm.bands_intact(a)
 
 
 def test_arena_keeps_the_strides_of_a_view_and_refuses_a_short_band():
