@@ -75,6 +75,8 @@ TRANSFORMS = Registry('transform')
 DATASETS = Registry('dataset')
 DATA_SAMPLERS = Registry('data sampler')
 METRICS = Registry('metric')
+VISUALIZERS = Registry('visualizer')
+HOOKS = Registry('hook')
 
 
 def mirror_into_mmengine():
